@@ -9,11 +9,15 @@ InternVideo2/single_modality/scripts/pretraining/1B_pt.sh) on synthetic random-p
 frame (mask ratio 0.8 -> L = 417), bf16 MFMA compute, per-GPU batch 128 by default (weak scaling; --batch 32 = the reference recipe's).  Inputs and the synthetic teacher
 targets are resident in HBM before the timed region; the mask -> gather-index compaction runs inside it.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+Prints ONE JSON line (rank 0) with the contract fields (metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of one
+timed step).  A plain run sets up, warms up, times the --steps steps and prints; everything else it can measure runs only with --full:
   roofline     : the dominant kernel (the bf16 MFMA GEMM family), achieved TFLOP/s from per-launch HIP events recorded on
                  the launch stream during the timed steps, against the 2.5 PFLOP/s dense bf16 MFMA peak of gfx950;
   cpu_baseline : the CPU oracle (oracle/, a port of the reference's unfused fp32 path) timed on this box's host cores on a
-                 bounded sample (rank 0, N = 1 only).
+                 bounded sample (rank 0, N = 1 only);
+  and the encoder share, other_kernels, the measured contention term, the B = 32 block and the `secondary` lines (B/14, stage 2).
+--dump-outputs DIR writes what the last timed step computed (dump_outputs below) as DIR/<name>.npy; the inputs and the initial weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -127,7 +131,16 @@ def parse():
                          "summed exactly -- what the reference's DeepSpeed bf16 engine does, and what keeps the W-rank step within the 1e-3 loss bar of "
                          "the single-rank step on the concatenated batch (tests/test_multiproc_gpu.py); bf16 halves the bytes on the wire and rounds the "
                          "W-way sum to bf16 inside RCCL")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what takes runs of its own: per-launch kernel events (roofline, other_kernels, encoder "
+                         "share), the contention term, the B = 32 block, the `secondary` lines and the CPU baseline (each still subject to its --no-* "
+                         "switch).  Off: the line carries the headline and what follows from it arithmetically")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32, ~32 MB): loss, loss parts, "
+                         "gradient norm, and the updated weights and gradients on a fixed seeded sample of elements")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.batch is None:
         args.batch = 16 if args.model == "6B" else 128
     return args
@@ -347,6 +360,45 @@ def droppath_account(model, steps, B, L, nominal_flop_per_clip):
                 executed_flop_per_clip=round(executed, 1), nominal_flop_per_clip=nominal_flop_per_clip,
                 skipped_flop_share=round(1.0 - executed / nominal_flop_per_clip, 4), branch_flop_per_clip_attn_mlp=[float(br[0]), float(br[1])],
                 how="kept (block, branch, sample) triples summed on the device inside every timed step (ops.droppath_plan counts)")
+
+
+DUMP_SAMPLE = 1 << 22              # elements of each sampled output of --dump-outputs (16 MiB of float32 each)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(out_dir, model, engine, loss, parts, sample=DUMP_SAMPLE, seed=DUMP_SEED):
+    """--dump-outputs: what the last timed step handed its caller, as float32 arrays in out_dir/<name>.npy --
+      loss.npy          [1]  the step's loss;          loss_parts.npy [3]  its (clip, final clip, mae) terms;
+      grad_norm.npy     [1]  the global gradient norm the step clipped with;
+      params_sample.npy [n]  the weights after the step's AdamW update, and grads_sample.npy [n] the step's gradients, both at the same n
+                             positions of the trainable parameters concatenated in model.named_parameters() order: sorted positions drawn
+                             with replacement from numpy's PCG64(seed), n = min(sample, #elements) (every element when the model is smaller).
+    Two builds run with the same arguments see the same inputs, initial weights and positions, so the files compare one to one."""
+    named = [(n, p) for n, p in model.named_parameters() if p.requires_grad]
+    sizes = np.array([p.numel() for _, p in named], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(offs[-1])
+    if total <= sample:
+        idx = np.arange(total, dtype=np.int64)
+    else:
+        idx = np.sort(np.random.Generator(np.random.PCG64(seed)).integers(0, total, sample, dtype=np.int64))
+    bounds = np.searchsorted(idx, offs)
+    w_parts, g_parts = [], []
+    for i, (_, p) in enumerate(named):
+        lo, hi = int(bounds[i]), int(bounds[i + 1])
+        if lo == hi:
+            continue
+        loc = torch.from_numpy(idx[lo:hi] - offs[i]).to(p.device)
+        w_parts.append(p.detach().reshape(-1)[loc].float())
+        g = getattr(p, "main_grad", None)
+        g = p.grad if g is None else g
+        g_parts.append(g.detach().reshape(-1)[loc].float() if g is not None else torch.full((hi - lo,), float("nan"), device=p.device))
+    arrays = {"loss": loss.detach().reshape(1), "loss_parts": torch.stack([t.detach().reshape(()) for t in parts]),
+              "grad_norm": engine.grad_norm.detach().reshape(-1)[:1], "params_sample": torch.cat(w_parts), "grads_sample": torch.cat(g_parts)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+    return sorted(arrays)
 
 
 def secondary_lines(timeout_s: float = 150.0):
@@ -584,11 +636,13 @@ def main():
     if args.dry_run:
         return _dry_run(args, _reserve_stdout())
     if args.model == "stage2-1B":                         # a different workload with its own metric name: the stage-2 bench tool's line
+        if args.dump_outputs:
+            sys.exit("bench.py: --dump-outputs covers the stage-1 student step (--model 1B / B14 / 6B), not --model stage2-1B")
         sys.path.insert(0, ROOT)
         from tools import bench_stage2
         sys.argv = ["bench_stage2.py", "--batch", str(64 if args.batch == 128 else args.batch), "--steps", str(args.steps), "--warmup", str(args.warmup),
                     "--batch-text", "--group-wgrad", "--engine", "--gpus", str(args.gpus), "--reduce-mode", args.reduce_mode] + ([] if args.no_graph else ["--graph"]) + \
-                   (["--no-cpu-baseline"] if args.no_cpu_baseline else []) + (["--share-gpu"] if args.share_gpu else [])
+                   (["--no-cpu-baseline"] if (args.no_cpu_baseline or not args.full) else []) + (["--share-gpu"] if args.share_gpu else [])
         return bench_stage2.main()
     json_fd = _reserve_stdout()
     spec = MODELS[args.model]
@@ -759,7 +813,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     graphed_any = graphed or dist_mode in ("graph", "graph-overlap", "graph-segments")
-    prof = None if (args.no_kernel_events or graphed_any) else []
+    kernel_events = args.full and not args.no_kernel_events
+    prof = None if (not kernel_events or graphed_any) else []
     kprof = None if prof is None else []
     eager_ms = None
     ops.GEMM_PROFILE, ops.KERNEL_PROFILE = prof, kprof
@@ -769,7 +824,7 @@ def main():
     host_step = []
     for _ in range(args.steps):
         th = time.perf_counter()
-        loss, _ = step()
+        loss, parts = step()
         host_step.append(time.perf_counter() - th)
     t_enqueued = time.perf_counter() - t0                      # host time to enqueue all steps (no sync inside a step)
     torch.cuda.synchronize()
@@ -783,10 +838,16 @@ def main():
     if dev.type == "cuda":
         hbm = {"peak_allocated_gb": round(torch.cuda.max_memory_allocated(dev) / 2 ** 30, 1), "reserved_gb": round(torch.cuda.memory_reserved(dev) / 2 ** 30, 1),
                "capacity_gb": round(torch.cuda.get_device_properties(dev).total_memory / 2 ** 30, 1), "at": "end of the timed region (before the B = 32 / secondary blocks)"}
+    dumped = None
+    if args.dump_outputs:                                        # before anything below runs more steps on the same engine
+        if engine.zero1:
+            engine.consolidate()                                 # collective: every rank's shards of the fp32 master weights
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, model, engine, loss, parts)
     dp = droppath_account(model, args.steps, B, L, spec["flop"])     # executed vs nominal FLOPs of the timed steps
     events_from, event_steps = "timed steps", args.steps
     marks = []                                                   # (label, event) at the encoder's boundaries of the eager event pass, if it runs
-    if graphed_any and not args.no_kernel_events:
+    if graphed_any and kernel_events:
         # HIP events cannot be recorded inside a graph replay: the per-launch GEMM events come from eager steps of the same
         # workload, run right after the timed region (they include the host-side launch gaps the graph removes)
         eager_step()                                             # untimed: the allocator refills its pools after graph mode
@@ -813,7 +874,7 @@ def main():
     # excluded) against the MFMA peak.  Its share of the step comes from HIP events at the encoder's boundaries in the eager pass above
     # (functional.STEP_MARKS); the share is applied to the timed (graph-replayed) step.
     encoder = None
-    if graphed_any and not args.no_kernel_events and args.model == "1B" and not args.with_teachers:
+    if graphed_any and kernel_events and args.model == "1B" and not args.with_teachers:
         try:
             lab = {}
             for name, ev in marks:
@@ -887,7 +948,7 @@ def main():
 
     # measured contention term of the scaling prediction (before the engine's graph is re-captured for the B = 32 block below)
     contention = None
-    if world == 1 and graphed and args.model == "1B" and not args.no_contention:
+    if args.full and world == 1 and graphed and args.model == "1B" and not args.no_contention:
         try:
             contention = comm_contention(engine, step, elapsed / args.steps * 1e3, dev)
         except Exception as e:       # noqa: BLE001
@@ -895,7 +956,7 @@ def main():
 
     # secondary block: the reference recipe's per-GPU batch (scripts/pretraining/1B_pt.sh:50), same engine, re-captured on B = 32 inputs
     b32 = None
-    if world == 1 and graphed and args.batch != 32 and args.model == "1B" and not args.no_b32:
+    if args.full and world == 1 and graphed and args.batch != 32 and args.model == "1B" and not args.no_b32:
         try:
             Bs = 32
             v32, m32 = video[:Bs].clone(), mask[:Bs].clone()
@@ -979,6 +1040,8 @@ def main():
             "b32": b32,
             "attn_kernel": {0: "auto (32x32x16 MFMA)", 1: "16x16x32 MFMA", 2: "32x32x16 MFMA"}[args.attn_kernel],
             "reduce": f"{args.reduce_mode}/{args.reduce_dtype}" if (world > 1 or args.force_dist) else "n/a",
+            "full": args.full,                                   # False: roofline / other_kernels / encoder / b32 / contention / secondary / cpu_baseline not run
+            "dumped_outputs": dumped,
         }
         if world > 1 or args.force_dist:
             out["scaling_model"] = scaling_model(engine, max(world, 1), elapsed / args.steps)
@@ -1002,9 +1065,9 @@ def main():
                     e *= strag["efficiency_factor"][n]
                 comb[n] = {"efficiency": round(e, 4), "speedup": round(int(n) * e, 3)}
             out["scaling_model_predictions"]["with_measured_contention_and_straggler_model"] = comb
-        if world == 1 and args.model == "1B" and not (args.no_secondary or args.with_teachers or args.fp8 or args.force_dist):
+        if args.full and world == 1 and args.model == "1B" and not (args.no_secondary or args.with_teachers or args.fp8 or args.force_dist):
             out["secondary"] = secondary_lines()
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 out["cpu_baseline"] = cpu_baseline(spec, args.cpu_iters)
             except Exception as e:       # never lose the GPU number to a host-side problem

@@ -594,8 +594,13 @@ class IVTrainEngine:
         self._graph = torch.cuda.CUDAGraph()
         Fn.WGRAD_KEEPALIVE = []
         Fn.FP8_CAPTURE_CACHE = {}                             # fp8 weights are quantised INSIDE the graph, once per captured step
+        # With a process group, other threads call into the runtime while the step is captured: the per-block hook issues the bucket
+        # collectives from autograd's device thread, and the group's watchdog polls the events of the warm-up steps' collectives.  A
+        # "global" capture subjects each such call to the capture in progress; the segmented capture runs "relaxed" for that reason,
+        # and so does this one.  (capture_comm=True with zero1 still dies inside capture_end on a 1-rank RCCL group: not explained by this.)
+        mode = "relaxed" if self.comm else "global"
         try:
-            with _cyclic_gc_paused(), torch.cuda.graph(self._graph):
+            with _cyclic_gc_paused(), torch.cuda.graph(self._graph, capture_error_mode=mode):
                 self._graph_out = body()
         finally:
             keep, Fn.WGRAD_KEEPALIVE = Fn.WGRAD_KEEPALIVE, None

@@ -1001,3 +1001,60 @@ def test_bench_counter_stamp_lookup(tmp_path):
     assert bench._stamped(str(path), "k<false>") is None and bench._stamped(str(tmp_path / "absent.json"), "k") is None
     path.write_text(json.dumps({"kernels": table, "source_digest": "0123456789abcdef"}))
     assert bench._stamped(str(path), "exact<1,0>")["matches_current_sources"] is False
+
+
+def test_bench_dump_outputs_writes_a_seeded_sample(tmp_path):
+    """bench.py --dump-outputs: the last timed step's loss, loss parts, gradient norm and a fixed seeded sample of the updated weights and of
+    the gradients, float32 .npy files; the sample positions follow the documented rule (sorted PCG64 draws over the trainable parameters in
+    named_parameters() order), so two runs -- or two builds -- write the same positions.  The 1B model's dump stays under 64 MB."""
+    import importlib.util
+    from types import SimpleNamespace
+    spec = importlib.util.spec_from_file_location("_bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    _, m = _tiny()
+    named = [(n, p) for n, p in m.named_parameters() if p.requires_grad]
+    for i, (_, p) in enumerate(named):
+        p.main_grad = torch.full(p.shape, float(i), dtype=torch.bfloat16 if p.dim() >= 2 else torch.float32)
+    eng = SimpleNamespace(grad_norm=torch.tensor([2.5]))
+    loss, parts = torch.tensor(1.25), (torch.tensor(0.5), torch.tensor(0.25), torch.tensor(0.5))
+    total = sum(p.numel() for _, p in named)
+    n = total // 3
+    names = bench.dump_outputs(str(tmp_path / "a"), m, eng, loss, parts, sample=n)
+    bench.dump_outputs(str(tmp_path / "b"), m, eng, loss, parts, sample=n)
+    assert names == ["grad_norm", "grads_sample", "loss", "loss_parts", "params_sample"]
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in names}
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert all(np.array_equal(got[k], np.load(tmp_path / "b" / f"{k}.npy")) for k in names)
+    assert got["loss"].tolist() == [1.25] and got["loss_parts"].tolist() == [0.5, 0.25, 0.5] and got["grad_norm"].tolist() == [2.5]
+    idx = np.sort(np.random.Generator(np.random.PCG64(bench.DUMP_SEED)).integers(0, total, n, dtype=np.int64))
+    flat = torch.cat([p.detach().reshape(-1) for _, p in named]).numpy()
+    owner = np.repeat(np.arange(len(named)), [p.numel() for _, p in named])
+    assert np.array_equal(got["params_sample"], flat[idx]) and np.array_equal(got["grads_sample"], owner[idx].astype(np.float32))
+    # a model smaller than the sample: every element, in order
+    bench.dump_outputs(str(tmp_path / "c"), m, eng, loss, parts, sample=total + 1)
+    assert np.array_equal(np.load(tmp_path / "c" / "params_sample.npy"), flat)
+    # the 1B student (1.07 G trainable parameters): two sampled arrays of DUMP_SAMPLE float32 values + a few scalars
+    assert 2 * 4 * bench.DUMP_SAMPLE + 64 < 64e6
+
+
+def test_bench_plain_run_and_its_options():
+    """--full is off by default (the plain run times the headline only), --dump-outputs takes a directory, and --steps must be at least 1:
+    the line's ms_per_step is the wall time of one of exactly --steps timed steps."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("_bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    argv = sys.argv
+    try:
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"]
+        a = bench.parse()
+        assert a.full is False and a.dump_outputs is None and a.steps == 3 and a.warmup == 1
+        sys.argv = ["bench.py", "--full", "--dump-outputs", "out_dir"]
+        a = bench.parse()
+        assert a.full is True and a.dump_outputs == "out_dir"
+        sys.argv = ["bench.py", "--steps", "0"]
+        with pytest.raises(SystemExit):
+            bench.parse()
+    finally:
+        sys.argv = argv

@@ -41,4 +41,4 @@ PY
 fi
 python tools/pmc_mfma.py $(find /tmp/mfmacal_$TAG -name "*counter_collection.csv" | head -1) $O/mfma_probe.json > $O/${TAG}_mfma_util.md 2>&1
 head -20 $O/${TAG}_mfma_util.md | cut -c1-200; cp profiles/pmc_mfma_util.json $O/${TAG}_pmc_mfma_util.json 2>/dev/null
-echo "== bench (carrying the stamped counters)"; timeout 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; cut -c1-300 $O/${TAG}_bench.json; tail -2 $O/${TAG}_bench.err
+echo "== bench (carrying the stamped counters)"; timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_bench.json 2> $O/${TAG}_bench.err; cut -c1-300 $O/${TAG}_bench.json; tail -2 $O/${TAG}_bench.err

@@ -11,6 +11,6 @@ for M in B14 stage2-1B; do
   DB=$(find /tmp/prof_${TAG}_$M -name "*.db" | head -1)
   if [ -n "$DB" ]; then python tools/rocpd_stats.py $DB > $O/${TAG}_${M}_kernel_stats.md 2>&1; fi
   head -30 $O/${TAG}_${M}_kernel_stats.md | cut -c1-220
-  python bench.py --model $M --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_${M}_bench.json 2> $O/${TAG}_${M}_bench.err
+  python bench.py --full --model $M --steps 6 --warmup 2 --no-cpu-baseline > $O/${TAG}_${M}_bench.json 2> $O/${TAG}_${M}_bench.err
   tail -c 400 $O/${TAG}_${M}_bench.err
 done
