@@ -106,6 +106,36 @@ int ivh_fp8_quantize(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, in
 int ivh_fp8_quantize_delayed(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
                              const float* amax_prev, float* scale_out, uint32_t* amax_next, void* stream);
 int ivh_gemm_fp8(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, void* stream);
+/* fp8 UNDER DropPath SKIPPING (device-side row counts; new entry points and new accepted descriptor fields, no signature or struct layout
+ * changed: the ABI version stays 2).
+ * ivh_fp8_quantize_dyn / ivh_fp8_quantize_delayed_dyn: as the two calls above with the row count in device memory (int32, 0 <= *m_dev <= M,
+ * never NULL): x holds the kept samples of a DropPath branch compacted to its front, the rows behind the count are stale memory.  The
+ * launches are sized for M.  Rows at or past *m_dev are not read -- neither by the amax pass nor by the amax_next collection of the delayed
+ * flavour, so that a stale NaN / Inf / large value behind the count can never reach the tensor's scale, now or on the next step -- and the
+ * rows of q at or past it are not written.  Transposed copy qt[K][ldt] (ldt >= M rounded up to 16): columns < *m_dev are written, columns
+ * *m_dev .. next multiple of 16 are ZERO-FILLED HERE (the choice between zero-filling in the quantiser and masking single columns in the
+ * GEMM: the GEMM's K mask works on 16-byte chunks, see k_dev below), columns from that multiple of 16 on are not written.
+ * *m_dev = 0 is legal: scale_out[0] = 1e-12 / 448 (the floor), amax_next unchanged, nothing else written.
+ * NOT bitwise the multiply-by-zero run (unlike bf16 skipping): the per-tensor amax is taken over the kept rows only, so the scale of a
+ * tensor -- and with it the rounding of every kept element -- can differ from the run that quantises all rows.  With every sample kept
+ * the two runs are bitwise equal.
+ * ivh_gemm_fp8 / ivh_gemm_fp8_cs with d->m_dev or d->k_dev: always the 256x256 e4m3 kernel, whatever the size (the size test of a plain
+ * launch, M * N >= 512^2 and K >= 512, is a speed heuristic; the kernel's K loop runs any K >= 1, so there is no structural K floor)
+ * and whatever ivh_set_gemm_fp8_kernel says.
+ *   m_dev: forward plain (+ bias), forward act = 1 / 3 (GELU; act = 3 with the gelu' copy in `preact`), dgrad plain, dgrad x dact_in
+ *          (act = 3).  Same contract as the bf16 kernels: workgroups without a tile leave at once, descriptors end at the last kept
+ *          row, rows behind the count are neither read nor written.  The x dact_in launch also accepts colsum_part (fp32
+ *          [2 * ceil(M / 256)][N], as in ivh_gemm_desc): the bias gradient of the layer in front; reduce with ivh_colsum_finish_dyn.
+ *   k_dev: the weight gradient dY^T x X^T on the transposed copies, contraction over the first *k_dev token columns (plain epilogue, no
+ *          bias).  Both operands must hold zeros from column *k_dev up to the next multiple of 16 (ivh_fp8_quantize*_dyn writes them);
+ *          nothing from there on is read.  *k_dev = 0 writes C = 0.
+ * Rejected with an error (never handed to the 128x128 kernel, which would walk the stale rows): fp32 output, act = 2, batch > 1, a
+ * pre-activation copy without act = 3, both counts at once, operands or outputs of 2 GiB or more.  No tail split:
+ * ivh_gemm_fp8_split_workspace answers 0 for such a descriptor. */
+int ivh_fp8_quantize_dyn(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
+                         float* scale_out, uint32_t* amax_scratch, const int32_t* m_dev, void* stream);
+int ivh_fp8_quantize_delayed_dyn(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
+                                 const float* amax_prev, float* scale_out, uint32_t* amax_next, const int32_t* m_dev, void* stream);
 /* Per-channel weight scales.  ivh_fp8_quantize_weight: W bf16 [N][K] (a Linear's weight, P:158-160 / 268-271) -> q e4m3 [N][K] with one
  * scale per ROW n (scale_rows[N]: the forward GEMM's B operand, output column n) and qt e4m3 [K][ldt] (ldt >= N rounded up to 16, pad
  * columns zero) with one scale per COLUMN k of W (scale_cols[K]: the dgrad GEMM's B operand W^T, output column k); a scale can leave a
@@ -115,7 +145,9 @@ int ivh_fp8_quantize_weight(const uint16_t* w, int64_t ld, int N, int K, uint8_t
                             float* scale_rows, float* scale_cols, uint32_t* amax_scratch, void* stream);
 int ivh_gemm_fp8_cs(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b_cols, void* stream);
 int64_t ivh_gemm_fp8_split_workspace(const ivh_gemm_desc* d);   /* as ivh_gemm_split_workspace, for ivh_gemm_fp8 */
-/* 0 = choose per problem (the persistent 256 x 256 e4m3 kernel for large problems), 1 = always the 128 x 128 e4m3 kernel (A/B, tests) */
+/* 0 = choose per problem (the persistent 256 x 256 e4m3 kernel for large problems), 1 = always the 128 x 128 e4m3 kernel (A/B, tests),
+ * 2 = always the 256 x 256 e4m3 kernel where the layout allows (tests: the counterpart of ivh_set_gemm_kernel(2)).  Count-carrying
+ * descriptors (m_dev / k_dev) run on the 256 x 256 kernel under every choice. */
 int ivh_set_gemm_fp8_kernel(int choice);
 /* Kernel selection for ivh_gemm_bf16: 0 = per-shape heuristic (default), 1 = 128x128 tile / 4-wave kernel,
  * 2 = 256x256 tile / 8-wave LDS-DMA ping-pong kernel.  Process-wide; meant for tests and benchmarks. */

@@ -304,9 +304,15 @@ __device__ __forceinline__ G2Tile g2_decode(int lin, int tiles_m, int tiles_n) {
 // *m_dev for forward / dgrad launches (fewer row tiles: workgroups whose first tile does not exist leave at once, descriptors end at the
 // last real row so that stale rows behind it are never read or written), *k_dev for weight gradients (shorter K loops; per problem in a
 // grouped launch).  A count of 0 is legal (every sample of the branch dropped): no tile runs / the weight gradient is written as zeros.
+// DYN && FP8 (single problem, whole tiles): *m_dev works as above with one byte per operand element.  *k_dev is the case the bf16 kernels do
+// not have: on the e4m3 path a weight gradient is dY^T x X^T with BOTH operands K-contiguous and the token rows along K, so no descriptor can
+// end at the count -- the per-lane K mask of the LDS-DMA requests (g2_issue: chunk start >= K -> out-of-range offset -> zeros) follows the
+// device value instead.  The mask works on 16-byte chunks: columns *k_dev .. next multiple of 16 of both operands must hold zeros, which
+// is what ivh_fp8_quantize*_dyn writes there; nothing from that multiple of 16 on is read.
 template <bool A_KC, bool B_KC, int EPI, bool GROUPED = false, int DBG = 0, int SCHED = 0, bool FP8 = false, bool SPLIT = false, bool HALF = false, bool DYN = false>
 __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
-  static_assert(!DYN || (!FP8 && !HALF && SCHED == 0 && DBG == 0), "device-side row counts: plain bf16 kernels (single problem, with or without the tail split, or grouped)");
+  static_assert(!DYN || (!HALF && SCHED == 0 && DBG == 0), "device-side row counts: plain kernels (single problem, with or without the tail split, or grouped)");
+  static_assert(!DYN || !FP8 || (!SPLIT && !GROUPED), "device-side row counts, e4m3 flavour: single problem, whole tiles");
   static_assert(!FP8 || (A_KC && B_KC && !GROUPED && SCHED == 0 && DBG == 0), "the e4m3 flavour is built for K-contiguous operands only");
   static_assert(!SPLIT || (!GROUPED && SCHED == 0 && DBG == 0), "the tail split is built for the plain single-problem kernels");
   static_assert(!HALF || (A_KC && !GROUPED && !SPLIT && !FP8 && SCHED == 0 && DBG == 0), "half-width tiles: bf16, K-contiguous A, plain single-problem kernels");
@@ -326,15 +332,15 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
       tiles_m = (M_rt + G2_BM - 1) / G2_BM;
       total = tiles_m * tiles_n;
       const int last = M_rt - 1;
-      a_bytes = M_rt > 0 ? (last * p.lda + K) * 2 : 0;
+      a_bytes = M_rt > 0 ? (last * p.lda + K) * ES : 0;
       c_bytes = M_rt > 0 ? (last * p.ldc + p.N) * 2 : 0;
       p_bytes = (M_rt > 0 && p.preact) ? (last * p.ldp + p.N) * 2 : 0;
       d_bytes = (M_rt > 0 && p.dact_in) ? (last * p.ldd + p.N) * 2 : 0;
     }
-    if (p.k_dev) {                                     // shorter contraction (rows-contiguous operands: [k][rows])
+    if (p.k_dev) {                                     // shorter contraction
       K = max(0, min(__builtin_amdgcn_readfirstlane(*p.k_dev), p.K));
-      a_bytes = K > 0 ? ((K - 1) * p.lda + p.M) * 2 : 0;
-      b_bytes = K > 0 ? ((K - 1) * p.ldb + p.N) * 2 : 0;
+      if constexpr (!A_KC) a_bytes = K > 0 ? ((K - 1) * p.lda + p.M) * 2 : 0;      // rows-contiguous operands [k][rows]: the descriptor ends at the count
+      if constexpr (!B_KC) b_bytes = K > 0 ? ((K - 1) * p.ldb + p.N) * 2 : 0;      // (K-contiguous, FP8: the per-lane K mask of g2_issue follows K)
     }
   }
   const int nk = (K + BKE - 1) / BKE;
@@ -1463,22 +1469,38 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
 
 
 // e4m3 operands (ivh_gemm_fp8, gemm_fp8.hip): bf16 output, K-contiguous operands, plain / GELU(+gelu') / x gelu' epilogues, problems
-// large enough for 256 x 256 tiles.  Returns 1 when the problem is not for this kernel (the caller uses the 128^2 e4m3 kernel).
-extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, void* stream) {
+// large enough for 256 x 256 tiles (`force`: any size -- the size test is a speed heuristic, the K loop runs any K >= 1, ghost K steps
+// multiply zeros).  Returns 1 when the problem is not for this kernel (the caller uses the 128^2 e4m3 kernel).
+// A descriptor that carries a device-side row count (m_dev / k_dev) runs here or nowhere: the 128^2 kernel would walk the stale rows behind
+// the count, so whatever this kernel is not built for is an error (< 0) for such a descriptor, never a 1.
+extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream) {
   using namespace ivh;
-  if (!d->a_kc || !d->b_kc || d->c_fp32 || d->batch > 1 || d->colsum_part || d->act == 2 || d->m_dev || d->k_dev) return 1;
-  if (d->dact_in && (d->act != 3 || d->preact)) return 1;
-  if (!d->dact_in && d->act == 1 && d->preact) return 1;
-  if (!d->dact_in && d->act == 0 && d->preact) return 1;
-  if ((long)d->M * d->N < 512L * 512 || d->K < 512) return 1;
+  const bool dyn = d->m_dev || d->k_dev;
+  if (dyn) {
+    IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm_fp8: m_dev and k_dev are mutually exclusive");
+    IVH_REQUIRE(d->a_kc && d->b_kc && !d->c_fp32 && d->batch <= 1 && d->act != 2,
+                "gemm_fp8: device-side row counts need the 256x256 e4m3 kernel: K-contiguous operands, bf16 output, batch 1, erf-GELU or plain epilogue");
+    IVH_REQUIRE(!(d->dact_in && (d->act != 3 || d->preact)) && !(!d->dact_in && d->act != 3 && d->preact),
+                "gemm_fp8: device-side row counts: a pre-activation copy exists with act = 3 (GELU + gelu' copy) only, x gelu' with act = 3 only");
+    IVH_REQUIRE(!d->k_dev || (!d->dact_in && d->act == 0 && !d->bias && !d->preact), "gemm_fp8: k_dev counts the token rows of a weight gradient (plain epilogue, no bias)");
+    IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in), "gemm_fp8: colsum_part is a by-product of the m_dev x gelu' dgrad launch");
+  } else {
+    if (!d->a_kc || !d->b_kc || d->c_fp32 || d->batch > 1 || d->colsum_part || d->act == 2) return 1;
+    if (d->dact_in && (d->act != 3 || d->preact)) return 1;
+    if (!d->dact_in && d->act == 1 && d->preact) return 1;
+    if (!d->dact_in && d->act == 0 && d->preact) return 1;
+    if (!force && ((long)d->M * d->N < 512L * 512 || d->K < 512)) return 1;
+  }
   const long lim = (1L << 31) - (1L << 24);
   const long a_bytes = ((long)d->M - 1) * d->lda + d->K, b_bytes = ((long)d->N - 1) * d->ldb + d->K;
   Gemm256Params p{};
   p.c_bytes = (((long)d->M - 1) * d->ldc + d->N) * 2;
   p.p_bytes = d->preact ? (((long)d->M - 1) * d->ldp + d->N) * 2 : 0;
   p.d_bytes = d->dact_in ? (((long)d->M - 1) * d->ldd + d->N) * 2 : 0;
-  if (a_bytes >= lim || b_bytes >= lim || p.c_bytes >= lim || p.p_bytes >= lim || p.d_bytes >= lim) return 1;
-  if (d->lda >= (1L << 31) || d->ldb >= (1L << 31) || d->ldc >= (1L << 31) || d->ldp >= (1L << 31) || d->ldd >= (1L << 31)) return 1;
+  const bool fits = a_bytes < lim && b_bytes < lim && p.c_bytes < lim && p.p_bytes < lim && p.d_bytes < lim &&
+                    d->lda < (1L << 31) && d->ldb < (1L << 31) && d->ldc < (1L << 31) && d->ldp < (1L << 31) && d->ldd < (1L << 31);
+  if (dyn) IVH_REQUIRE(fits, "gemm_fp8: device-side row counts: every operand / output must stay below 2 GiB (32-bit descriptor offsets)");
+  if (!fits) return 1;
   p.A = d->A; p.B = d->B; p.lda = (int)d->lda; p.ldb = (int)d->ldb; p.M = d->M; p.N = d->N; p.K = d->K;
   p.C = d->C; p.ldc = (int)d->ldc; p.c_fp32 = 0; p.bias = d->bias; p.act = d->act;
   p.preact = d->preact; p.ldp = (int)d->ldp; p.dact_in = d->dact_in; p.ldd = (int)d->ldd;
@@ -1498,6 +1520,16 @@ extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale
   const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
   hipStream_t s = (hipStream_t)stream;
   const int epi = d->dact_in ? 3 : (d->act ? 2 : 0);
+  if (dyn) {                                              // device-side row counts (DYN kernels): whole tiles, no tail split
+    p.m_dev = d->m_dev; p.k_dev = d->k_dev;
+    p.colsum_part = (epi == 3) ? d->colsum_part : nullptr;
+    p.split_main = p.total_tiles;
+    dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
+    if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
+    else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
+    else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
+    return ivh_host::check_launch("gemm256_fp8 (device-side row count)") ? -1 : 0;
+  }
   if (g2_apply_split(d, 1, p, cap, s)) {
     dim3 grid((unsigned)(p.total_tiles < cap ? p.total_tiles : cap), 1, 1), block(512);
     if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, true>), grid, block, 0, s, p);

@@ -158,7 +158,14 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(GemmF8Params p) {
 }
 
 // ---- quantisation: bf16 [M][K] -> e4m3 [M][K] (+ transposed copy [K][ldt], ldt >= M, pad columns zero) with ONE per-tensor scale ------------
-__global__ __launch_bounds__(256) void f8_amax_kernel(const bf16_t* __restrict__ x, long ld, int M, int K, unsigned* __restrict__ amax_bits) {
+// m_dev != NULL (the *_dyn entry points): the tensor has *m_dev <= M rows -- the kept samples of a DropPath branch, compacted to the front of
+// a buffer whose rows behind the count are stale memory.  Every kernel below then stops at the count: a stale NaN / Inf / large value there
+// would otherwise set the scale of the whole tensor through the NaN-sticky maximum.
+__device__ __forceinline__ int f8_rows(int M, const int* __restrict__ m_dev) { return m_dev ? max(0, min(m_dev[0], M)) : M; }
+
+__global__ __launch_bounds__(256) void f8_amax_kernel(const bf16_t* __restrict__ x, long ld, int M, int K, unsigned* __restrict__ amax_bits,
+                                                      const int* __restrict__ m_dev) {
+  M = f8_rows(M, m_dev);
   // NaN / Inf must survive: fmaxf drops NaN operands, and a finite amax would quantise a NaN element to a finite value -- every fp8
   // GEMM would then launder a diverged activation and the per-step NaN guard of the engine (engine_for_pretraining.py:151-161) could
   // never fire.  |x| is tracked so that NaN sticks, and reduced on the bit patterns (non-negative floats, Inf and NaN order like
@@ -195,8 +202,10 @@ __device__ __forceinline__ unsigned f8_pack4(float a, float b, float c, float d)
 // (one atomicMax per wave) for the next step, so the tensor is read once instead of twice.  Values beyond the stale range saturate at +-448.
 __global__ __launch_bounds__(256) void f8_quantize_kernel(const bf16_t* __restrict__ x, long ld, int M, int K, const unsigned* __restrict__ amax_bits,
                                                           uint8_t* __restrict__ q, long ldq, uint8_t* __restrict__ qt, long ldt, int Mt,
-                                                          float* __restrict__ scale_out, unsigned* __restrict__ amax_next) {
+                                                          float* __restrict__ scale_out, unsigned* __restrict__ amax_next, const int* __restrict__ m_dev) {
   __shared__ __attribute__((aligned(16))) uint8_t tile[64][80];           // [row][k] e4m3, 16-byte aligned rows
+  if (m_dev) { M = f8_rows(M, m_dev); Mt = qt ? ((M + 15) >> 4) << 4 : 0; }   // device-side row count: rows >= M neither read nor written,
+                                                                              // qt columns M .. Mt - 1 zero-filled, columns >= Mt untouched
   const float amax_raw = __uint_as_float(amax_bits[0]);
   const float amax = (amax_raw != amax_raw) ? amax_raw : fmaxf(amax_raw, 1e-12f);      // NaN stays NaN (Inf stays Inf): the scale poisons the product
   const float scale = amax / F8_MAX;                   // dequantisation multiplier
@@ -357,10 +366,10 @@ extern "C" int ivh_fp8_quantize(const uint16_t* x, int64_t ld, int M, int K, uin
   if (hipMemsetAsync(amax_scratch, 0, 4, s) != hipSuccess) { ivh_host::set_error("fp8_quantize: memset failed"); return -2; }
   long blocks = ((long)M * (K / 8) + 255) / 256;
   if (blocks > 2048) blocks = 2048;
-  hipLaunchKernelGGL(f8_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (long)ld, M, K, amax_scratch);
+  hipLaunchKernelGGL(f8_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (long)ld, M, K, amax_scratch, (const int*)nullptr);
   const int Mt = qt ? (int)(((M + 15) / 16) * 16) : 0;
   dim3 grid((K + 63) / 64, (M + 63) / 64, 1);
-  hipLaunchKernelGGL(f8_quantize_kernel, grid, dim3(256), 0, s, x, (long)ld, M, K, amax_scratch, q, (long)ldq, qt, (long)ldt, Mt, scale_out, (unsigned*)nullptr);
+  hipLaunchKernelGGL(f8_quantize_kernel, grid, dim3(256), 0, s, x, (long)ld, M, K, amax_scratch, q, (long)ldq, qt, (long)ldt, Mt, scale_out, (unsigned*)nullptr, (const int*)nullptr);
   return ivh_host::check_launch("fp8_quantize");
 }
 
@@ -374,8 +383,41 @@ extern "C" int ivh_fp8_quantize_delayed(const uint16_t* x, int64_t ld, int M, in
   const int Mt = qt ? (int)(((M + 15) / 16) * 16) : 0;
   dim3 grid((K + 63) / 64, (M + 63) / 64, 1);
   hipLaunchKernelGGL(f8_quantize_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, M, K, reinterpret_cast<const unsigned*>(amax_prev), q, (long)ldq, qt,
-                     (long)ldt, Mt, scale_out, amax_next);
+                     (long)ldt, Mt, scale_out, amax_next, (const int*)nullptr);
   return ivh_host::check_launch("fp8_quantize_delayed");
+}
+
+// ---- the same with the row count in device memory (DropPath skipping: include/internvideo_hip.h, "fp8 under DropPath skipping") -------------
+// The launches are sized for M; every kernel reads *m_dev and stops there.  *m_dev = 0: amax = 0, the scale is the 1e-12 / 448 floor, nothing
+// else is written.
+extern "C" int ivh_fp8_quantize_dyn(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
+                                    float* scale_out, uint32_t* amax_scratch, const int32_t* m_dev, void* stream) {
+  IVH_REQUIRE(x && q && scale_out && amax_scratch && m_dev && M > 0 && K > 0, "fp8_quantize_dyn: bad args");
+  IVH_REQUIRE(K % 8 == 0 && ld % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)m_dev % 4) == 0,
+              "fp8_quantize_dyn: K, ld multiples of 8, ldq multiple of 16, 16-byte aligned buffers, 4-byte aligned count");
+  IVH_REQUIRE(!qt || (ldt % 16 == 0 && ldt >= ((M + 15) / 16) * 16 && ((uintptr_t)qt % 16) == 0),
+              "fp8_quantize_dyn: transposed copy needs ldt >= M rounded up to 16 and 16-byte alignment");
+  hipStream_t s = (hipStream_t)stream;
+  if (hipMemsetAsync(amax_scratch, 0, 4, s) != hipSuccess) { ivh_host::set_error("fp8_quantize_dyn: memset failed"); return -2; }
+  long blocks = ((long)M * (K / 8) + 255) / 256;
+  if (blocks > 2048) blocks = 2048;
+  hipLaunchKernelGGL(f8_amax_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, (long)ld, M, K, amax_scratch, m_dev);
+  dim3 grid((K + 63) / 64, (M + 63) / 64, 1);
+  hipLaunchKernelGGL(f8_quantize_kernel, grid, dim3(256), 0, s, x, (long)ld, M, K, amax_scratch, q, (long)ldq, qt, (long)ldt, 0, scale_out, (unsigned*)nullptr, m_dev);
+  return ivh_host::check_launch("fp8_quantize_dyn");
+}
+
+extern "C" int ivh_fp8_quantize_delayed_dyn(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
+                                            const float* amax_prev, float* scale_out, uint32_t* amax_next, const int32_t* m_dev, void* stream) {
+  IVH_REQUIRE(x && q && scale_out && amax_prev && amax_next && m_dev && M > 0 && K > 0, "fp8_quantize_delayed_dyn: bad args");
+  IVH_REQUIRE(K % 8 == 0 && ld % 8 == 0 && ldq % 16 == 0 && ((uintptr_t)x % 16) == 0 && ((uintptr_t)q % 16) == 0 && ((uintptr_t)m_dev % 4) == 0,
+              "fp8_quantize_delayed_dyn: K, ld multiples of 8, ldq multiple of 16, 16-byte aligned buffers, 4-byte aligned count");
+  IVH_REQUIRE(!qt || (ldt % 16 == 0 && ldt >= ((M + 15) / 16) * 16 && ((uintptr_t)qt % 16) == 0),
+              "fp8_quantize_delayed_dyn: transposed copy needs ldt >= M rounded up to 16 and 16-byte alignment");
+  dim3 grid((K + 63) / 64, (M + 63) / 64, 1);
+  hipLaunchKernelGGL(f8_quantize_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, (long)ld, M, K, reinterpret_cast<const unsigned*>(amax_prev), q, (long)ldq, qt,
+                     (long)ldt, 0, scale_out, amax_next, m_dev);
+  return ivh_host::check_launch("fp8_quantize_delayed_dyn");
 }
 
 extern "C" int ivh_fp8_quantize_weight(const uint16_t* w, int64_t ld, int N, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
@@ -394,14 +436,17 @@ extern "C" int ivh_fp8_quantize_weight(const uint16_t* w, int64_t ld, int N, int
   return ivh_host::check_launch("fp8_quantize_weight");
 }
 
-extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, void* stream);   // gemm256.hip
-static int g_f8_kernel = 0;                               // 0 = per problem (256^2 when it applies), 1 = always the 128^2 kernel (A/B, tests)
-extern "C" int ivh_set_gemm_fp8_kernel(int choice) { g_f8_kernel = choice == 1 ? 1 : 0; return 0; }
+extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream);   // gemm256.hip
+// 0 = per problem (256^2 when it applies), 1 = always the 128^2 kernel (A/B, tests), 2 = always the 256^2 kernel where the layout allows (tests:
+// the reference launch of a bitwise comparison with a count-carrying one must run on the same kernel at fixture sizes)
+static int g_f8_kernel = 0;
+extern "C" int ivh_set_gemm_fp8_kernel(int choice) { g_f8_kernel = (choice == 1 || choice == 2) ? choice : 0; return 0; }
 
 extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8);      // gemm256.hip
 // bytes of d->split_ws with which ivh_gemm_fp8 would cut the tiles of a mostly empty last round into K slices (0 = no use)
 extern "C" int64_t ivh_gemm_fp8_split_workspace(const ivh_gemm_desc* d) {
-  if (!d || g_f8_kernel == 1 || !d->a_kc || !d->b_kc || (long)d->M * d->N < 512L * 512 || d->K < 512) return 0;
+  if (!d || g_f8_kernel == 1 || !d->a_kc || !d->b_kc || d->m_dev || d->k_dev) return 0;      // (count-carrying launches run whole tiles only)
+  if (g_f8_kernel != 2 && ((long)d->M * d->N < 512L * 512 || d->K < 512)) return 0;
   return ivh_gemm256_split_ws_bytes(d, 1);
 }
 
@@ -420,10 +465,19 @@ static int gemm_fp8_impl(const ivh_gemm_desc* d, const float* scale_a, const flo
   IVH_REQUIRE(d->K % 16 == 0 && d->lda % 16 == 0 && d->ldb % 16 == 0, "gemm_fp8: K, lda, ldb must be multiples of 16 (bytes)");
   IVH_REQUIRE(d->N % 8 == 0 && d->ldc % 4 == 0, "gemm_fp8: N multiple of 8, ldc multiple of 4");
   IVH_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && ((uintptr_t)d->C % 16) == 0, "gemm_fp8: base pointers must be 16-byte aligned");
-  IVH_REQUIRE(d->act >= 0 && d->act <= 3 && (d->batch <= 1) && !d->colsum_part, "gemm_fp8: unsupported activation / batch / colsum request");
+  IVH_REQUIRE(d->act >= 0 && d->act <= 3 && (d->batch <= 1), "gemm_fp8: unsupported activation / batch");
+  IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in && d->act == 3),
+              "gemm_fp8: colsum_part is a by-product of the count-carrying (m_dev) x gelu' dgrad launch only");
+  if (d->m_dev || d->k_dev) {                              // device-side row counts: the 256 x 256 kernel is the only one that stops at them
+    IVH_REQUIRE(scale_a && scale_b, "gemm_fp8: null scale");
+    IVH_REQUIRE(((uintptr_t)d->m_dev % 4) == 0 && ((uintptr_t)d->k_dev % 4) == 0, "gemm_fp8: m_dev / k_dev must be 4-byte aligned");
+    const int rc = ivh_gemm256_fp8_launch(d, scale_a, scale_b, scale_b_vec, 1, stream);
+    IVH_REQUIRE(rc != 1, "gemm_fp8: device-side row counts (m_dev / k_dev) need the 256x256 e4m3 kernel");
+    return rc;
+  }
   if (g_f8_kernel != 1) {                                  // large problems: the persistent 256 x 256 ping-pong kernel (gemm256.hip, FP8 flavour)
     IVH_REQUIRE(scale_a && scale_b, "gemm_fp8: null scale");
-    const int rc = ivh_gemm256_fp8_launch(d, scale_a, scale_b, scale_b_vec, stream);
+    const int rc = ivh_gemm256_fp8_launch(d, scale_a, scale_b, scale_b_vec, g_f8_kernel == 2, stream);
     if (rc <= 0) return rc;
   }
   GemmF8Params p;

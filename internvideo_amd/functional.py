@@ -465,14 +465,15 @@ class Fp8History:
         self.ready |= self.collected
         self.collected = set()
 
-    def quantize(self, key, x: torch.Tensor, want_transposed: bool):
+    def quantize(self, key, x: torch.Tensor, want_transposed: bool, m_dev: Optional[torch.Tensor] = None):
+        """m_dev: x holds *m_dev rows (DropPath skipping); the recorded max|x| is taken over them alone"""
         i = self.slot.setdefault(key, len(self.slot))
         if i >= self.cur.numel():
             raise RuntimeError("Fp8History: more quantisation sites than slots")
         self.collected.add(i)
         if i in self.ready:
-            return ops.fp8_quantize(x, want_transposed=want_transposed, amax_prev=self.cur[i:i + 1], amax_next=self.nxt[i:i + 1])
-        return ops.fp8_quantize(x, want_transposed=want_transposed, amax_next=self.nxt[i:i + 1])
+            return ops.fp8_quantize(x, want_transposed=want_transposed, amax_prev=self.cur[i:i + 1], amax_next=self.nxt[i:i + 1], m_dev=m_dev)
+        return ops.fp8_quantize(x, want_transposed=want_transposed, amax_next=self.nxt[i:i + 1], m_dev=m_dev)
 
 
 FP8_LINEAR_CHANNEL_SCALES = False       # Fp8LinearFn: per-channel weight scales (the block stack takes the switch from its meta)
@@ -608,9 +609,15 @@ DROPPATH_SKIP = __import__("os").environ.get("IVH_DROPPATH_SKIP", "1") != "0"
 def dp_skip_applies(meta, M: int, D: int, params) -> bool:
     """can this block stack run its DropPath branches on the kept samples only?  Needs the kernels that take device-side counts: the 256^2
     bf16 GEMM (operands below 2 GiB, erf-GELU with the derivative exchanged) and the 32x32 attention kernels (head dim <= 128, 16-byte
-    strides) -- otherwise the stack silently keeps the multiply-by-zero path (same results)."""
+    strides) -- otherwise the stack silently keeps the multiply-by-zero path (same results).
+    meta["fp8"]: the quantisers and the 256^2 e4m3 GEMM take the counts too (ops.fp8_quantize / ops.gemm_fp8, m_dev / k_dev); their
+    conditions are widths that are multiples of 16 and operands below 2 GiB (the bf16 outputs are the larger side of that bound; the e4m3
+    kernel's K loop has no structural K floor).  "auto" also asks for D >= 512 then: the fp8 launch's own size heuristic keeps a GEMM with
+    M * N < 512^2 or K < 512 on the 128^2 e4m3 kernel, a count-carrying launch always runs on the 256^2 one, and M * D >= 512^2 alone
+    covers M * N but not K >= 512 when D < 512 -- "auto" must not move such a GEMM to the other kernel.  Unlike bf16, fp8 skipping is not
+    bitwise the multiply-by-zero run: the per-tensor amax is taken over the kept rows only, so scales can differ."""
     mode = meta.get("dp_skip", "auto")
-    if not DROPPATH_SKIP or mode is False or mode is None or meta.get("fp8"):
+    if not DROPPATH_SKIP or mode is False or mode is None:
         return False
     if _act_d(meta["act"]) != "gelu_erf_d":
         return False
@@ -621,6 +628,11 @@ def dp_skip_applies(meta, M: int, D: int, params) -> bool:
     widest = max(3 * D, int(params[8].shape[0]))                                             # qkv / fc1 output widths
     if M * widest * 2 >= (1 << 31) - (1 << 24):
         return False
+    if meta.get("fp8"):
+        if D % 16 or int(params[8].shape[0]) % 16:           # qkv (3 D), proj (D), fc1 / fc2 (hidden): K, lda, ldb of every e4m3 GEMM
+            return False
+        if mode is not True and D < 512:
+            return False
     return mode is True or M * D >= 512 * 512               # "auto": small stacks stay on the per-shape kernel choice (128^2 GEMM tiles)
 
 
@@ -656,11 +668,11 @@ class BlockStackFn(torch.autograd.Function):
             transposed fp8 copy of x is what the weight gradient contracts over, so it is saved instead of the bf16 activation"""
             if not fp8:
                 return ops.gemm(x, mat(w), bias=bias, act=act_, want_preact=want_preact, m_dev=m_dev)
-            hist = meta.get("fp8_hist")
-            xq, xqt, sx = hist.quantize((i, name), x, True) if hist is not None else ops.fp8_quantize(x, want_transposed=True)
+            hist = meta.get("fp8_hist")                         # m_dev: only the kept rows are quantised, xqt is the compacted transposed copy
+            xq, xqt, sx = hist.quantize((i, name), x, True, m_dev) if hist is not None else ops.fp8_quantize(x, want_transposed=True, m_dev=m_dev)
             wq, _, sw, _ = fp8_weight(w, bool(meta.get("fp8_wchan")))
             q8[name] = (xqt, sx)
-            return ops.gemm_fp8(xq, wq, sx, sw, bias=bias, act=act_, want_preact=want_preact)
+            return ops.gemm_fp8(xq, wq, sx, sw, bias=bias, act=act_, want_preact=want_preact, m_dev=m_dev)
 
         if branch is None:
             res1 = res
@@ -761,16 +773,23 @@ class BlockStackFn(torch.autograd.Function):
                     dx, cs = ops.gemm(dy, mat(w), a_kc=True, b_kc=False, m_dev=m_dev), None
                 return dx, _wgrad_defer(dy, x, w, m_dev), cs
             hist = meta.get("fp8_hist")                                  # one quantisation feeds dgrad (plain) and wgrad (transposed copy)
-            dyq, dyqt, sd = hist.quantize((i, "d:" + name), dy, True) if hist is not None else ops.fp8_quantize(dy, want_transposed=True)
+            dyq, dyqt, sd = hist.quantize((i, "d:" + name), dy, True, m_dev) if hist is not None else ops.fp8_quantize(dy, want_transposed=True, m_dev=m_dev)
             _, wqt, _, sw = fp8_weight(w, bool(meta.get("fp8_wchan")))
-            dx = ops.gemm_fp8(dyq, wqt, sd, sw, k=dy.shape[1], dact_in=dact, act=(act if dact is not None else None))
+            cs = None
+            if dact is not None and m_dev is not None:                    # DropPath skipping: the fc1 bias gradient falls out of this epilogue
+                dx, cs = ops.gemm_fp8(dyq, wqt, sd, sw, k=dy.shape[1], dact_in=dact, act=act, m_dev=m_dev, want_colsum=True)
+            else:
+                dx = ops.gemm_fp8(dyq, wqt, sd, sw, k=dy.shape[1], dact_in=dact, act=(act if dact is not None else None), m_dev=m_dev)
             xqt, sx = q8[name]
             mg = getattr(w, "main_grad", None)
             if mg is None and not w.requires_grad:                        # frozen weight: autograd would discard the product
-                return dx, None, None
+                return dx, None, cs
             out = mg.view(w.shape[0], -1) if (mg is not None and mg.dtype in (BF16, F32)) else None
-            gw = ops.gemm_fp8(dyqt, xqt, sd, sx, out=out, out_fp32=(out is not None and out.dtype == F32))
-            return dx, (None if out is not None else _ret_grad(w, gw)), None
+            if m_dev is not None and out is not None and out.dtype == F32:    # the count-carrying kernel writes bf16: widen afterwards
+                out.copy_(ops.gemm_fp8(dyqt, xqt, sd, sx, k_dev=m_dev))
+                return dx, None, cs
+            gw = ops.gemm_fp8(dyqt, xqt, sd, sx, out=out, out_fp32=(out is not None and out.dtype == F32), k_dev=m_dev)
+            return dx, (None if out is not None else _ret_grad(w, gw)), cs
 
         pending_hooks: List[int] = []
         resolve_end_pending()                                                   # engine mode: the text / fusion tower's queued weight gradients

@@ -216,28 +216,50 @@ FP8 = torch.float8_e4m3fn
 
 
 def fp8_quantize(x: torch.Tensor, want_transposed: bool = False, amax_prev: Optional[torch.Tensor] = None,
-                 amax_next: Optional[torch.Tensor] = None):
+                 amax_next: Optional[torch.Tensor] = None, m_dev: Optional[torch.Tensor] = None,
+                 out: Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]] = None):
     """x bf16 [M, K] -> (q e4m3 [M, K], qt e4m3 [K, M16] | None, scale fp32 [1]) with one scale per tensor: x ~ q * scale.
     qt is the transposed copy (M16 = M rounded up to 16, pad columns zero) that dgrad / wgrad contract over.
     Current scaling (default): scale = max|x| / 448, two passes over x.  Delayed scaling: `amax_prev` (fp32 [1] in HBM: the amax this call
     site saw on the previous step) sets the scale, this call's max|x| is max-ed into `amax_next` (int32 [1], the bit pattern; the caller
-    zeroes it once per step): one pass over x.  With only `amax_next` given the call scales by its own amax and records it there."""
+    zeroes it once per step): one pass over x.  With only `amax_next` given the call scales by its own amax and records it there.
+    m_dev (int32 [1] in HBM, DropPath skipping): x holds *m_dev <= M rows, the rest is stale memory -- rows at or past the count are not read
+    (the amax, this step's and the recorded one, is taken over the kept rows only) and not written; qt gets its columns < *m_dev, zeros up to
+    the next multiple of 16 and nothing behind that (ivh_fp8_quantize_dyn).  out = (q, qt | None): write into these buffers (tests)."""
     _L.require_gpu()
     _chk(x, BF16, "x")
     if x.dim() != 2:
         raise InternVideoHipError("fp8_quantize: 2-D input")
     M, K = x.shape
-    q = torch.empty((M, K), dtype=FP8, device=x.device)
-    qt = torch.empty((K, (M + 15) // 16 * 16), dtype=FP8, device=x.device) if want_transposed else None
+    M16 = (M + 15) // 16 * 16
+    if out is not None:
+        q, qt = out
+        if q.dtype != FP8 or tuple(q.shape) != (M, K) or not q.is_cuda or q.stride(1) != 1:
+            raise InternVideoHipError(f"fp8_quantize: out[0] must be float8_e4m3fn {(M, K)} in HBM")
+        if want_transposed and (qt is None or qt.dtype != FP8 or tuple(qt.shape) != (K, M16) or not qt.is_cuda or qt.stride(1) != 1):
+            raise InternVideoHipError(f"fp8_quantize: out[1] must be float8_e4m3fn {(K, M16)} in HBM")
+        qt = qt if want_transposed else None
+    else:
+        q = torch.empty((M, K), dtype=FP8, device=x.device)
+        qt = torch.empty((K, M16), dtype=FP8, device=x.device) if want_transposed else None
     scale = torch.empty((1,), dtype=F32, device=x.device)
+    md = _cnt(m_dev, "m_dev") if m_dev is not None else None
     if amax_prev is not None:
         if amax_next is None or amax_prev.dtype != F32 or amax_next.dtype != torch.int32 or amax_prev.numel() != 1 or amax_next.numel() != 1:
             raise InternVideoHipError("fp8_quantize: delayed scaling needs amax_prev fp32 [1] and amax_next int32 [1]")
+        if md is not None:
+            call("ivh_fp8_quantize_delayed_dyn", ptr(x), x.stride(0), M, K, ptr(q), q.stride(0), ptr(qt), (qt.stride(0) if qt is not None else 0),
+                 ptr(amax_prev), ptr(scale), ptr(amax_next), ptr(md), stream_ptr())
+            return q, qt, scale
         call("ivh_fp8_quantize_delayed", ptr(x), x.stride(0), M, K, ptr(q), q.stride(0), ptr(qt), (qt.stride(0) if qt is not None else 0),
              ptr(amax_prev), ptr(scale), ptr(amax_next), stream_ptr())
         return q, qt, scale
     scratch = torch.empty((1,), dtype=torch.int32, device=x.device)
-    call("ivh_fp8_quantize", ptr(x), x.stride(0), M, K, ptr(q), q.stride(0), ptr(qt), (qt.stride(0) if qt is not None else 0), ptr(scale), ptr(scratch), stream_ptr())
+    if md is not None:
+        call("ivh_fp8_quantize_dyn", ptr(x), x.stride(0), M, K, ptr(q), q.stride(0), ptr(qt), (qt.stride(0) if qt is not None else 0), ptr(scale), ptr(scratch),
+             ptr(md), stream_ptr())
+    else:
+        call("ivh_fp8_quantize", ptr(x), x.stride(0), M, K, ptr(q), q.stride(0), ptr(qt), (qt.stride(0) if qt is not None else 0), ptr(scale), ptr(scratch), stream_ptr())
     if amax_next is not None:                               # first sighting of a call site: remember its amax for the next step
         amax_next.copy_(scratch)
     return q, qt, scale
@@ -262,16 +284,22 @@ def fp8_quantize_weight(w: torch.Tensor):
 
 
 def set_gemm_fp8_kernel(choice: int) -> None:
-    """0 = per problem (the persistent 256^2 e4m3 kernel for large problems), 1 = always the 128^2 e4m3 kernel (tests / benchmarks)"""
+    """0 = per problem (the persistent 256^2 e4m3 kernel for large problems), 1 = always the 128^2 e4m3 kernel, 2 = always the 256^2 e4m3
+    kernel where the layout allows (tests / benchmarks).  Launches with m_dev / k_dev run on the 256^2 kernel under every choice."""
     call("ivh_set_gemm_fp8_kernel", int(choice))
 
 
 def gemm_fp8(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: torch.Tensor, *, bias: Optional[torch.Tensor] = None, act=None,
              want_preact: bool = False, dact_in: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_fp32: bool = False,
-             alpha: float = 1.0, k: Optional[int] = None):
+             alpha: float = 1.0, k: Optional[int] = None, m_dev: Optional[torch.Tensor] = None, k_dev: Optional[torch.Tensor] = None,
+             want_colsum: bool = False):
     """C[m,n] = epi(alpha * scale_a * scale_b * sum_k a[m,k] b[n,k]); a [M, K*], b [N, K*] e4m3 (K-contiguous), contraction over the first
     `k` columns (default: all; the transposed copies of fp8_quantize carry zero pad columns, so contracting over all of them is exact).
-    scale_b with more than one element = one scale per row of b (per output column n: fp8_quantize_weight), length N."""
+    scale_b with more than one element = one scale per row of b (per output column n: fp8_quantize_weight), length N.
+    m_dev / k_dev (int32 [1] in HBM, DropPath skipping): the real row count of a / out (forward, dgrad) or the real contraction length (the
+    weight gradient on the transposed copies of fp8_quantize(..., m_dev=)); always the 256^2 e4m3 kernel, rows at or past *m_dev of `out`
+    and of the gelu' copy are left untouched.  want_colsum (with m_dev and dact_in): -> (out, part) with the bias-gradient partials of the
+    layer in front, for colsum_finish(part, m_dev=)."""
     _L.require_gpu()
     if a.dtype != FP8 or b.dtype != FP8 or a.dim() != 2 or b.dim() != 2:
         raise InternVideoHipError("gemm_fp8: a, b must be 2-D float8_e4m3fn")
@@ -303,15 +331,30 @@ def gemm_fp8(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: t
     if dact_in is not None:
         _chk(dact_in, BF16, "dact_in")
         d.dact_in, d.ldd = dact_in.data_ptr(), dact_in.stride(0)
+    dyn = None
+    if m_dev is not None:
+        d.m_dev = _cnt(m_dev, "m_dev").data_ptr()
+        dyn = (m_dev, M)
+    if k_dev is not None:
+        d.k_dev = _cnt(k_dev, "k_dev").data_ptr()
+        dyn = (k_dev, K)
+    part = None
+    if want_colsum:
+        if m_dev is None or dact_in is None:
+            raise InternVideoHipError("gemm_fp8: want_colsum is a by-product of the m_dev x gelu' dgrad launch")
+        part = torch.empty((2 * ((M + 255) // 256), N), dtype=F32, device=a.device)
+        d.colsum_part = part.data_ptr()
     ws = _attach_split_ws(d, out.device, "ivh_gemm_fp8_split_workspace")    # noqa: F841
     if GEMM_PROFILE is not None:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
         call(entry, C.byref(d), ptr(scale_a), ptr(scale_b), stream_ptr())
         e1.record()
-        GEMM_PROFILE.append((8, 1, 1, 2.0 * M * N * K, e0, e1))
+        GEMM_PROFILE.append((8, 1, 1, 2.0 * M * N * K, e0, e1) + ((dyn,) if dyn is not None else ()))
     else:
         call(entry, C.byref(d), ptr(scale_a), ptr(scale_b), stream_ptr())
+    if want_colsum:
+        return ((out, pre) if want_preact else out), part
     return (out, pre) if want_preact else out
 
 
