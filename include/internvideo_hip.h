@@ -453,6 +453,13 @@ int ivh_clip_coef(const float* sumsq, float max_norm, float* coef, float* norm_o
  * bf16 -> fp32.  Replaces the fp32 gradient accumulation of DeepSpeed's ZeRO-1 reduce-scatter (single_modality/utils.py:863-871,
  * scripts/pretraining/1B_pt.sh:65).  chunk: multiple of 8 elements; both buffers 16-byte aligned. */
 int ivh_shard_sum_bf16(const uint16_t* in, int W, int64_t chunk, float* out, void* stream);
+/* The same sum on top of what `out` already holds: acc = accumulate ? out[i] : 0, then += float(in[r * chunk + i]) for r ascending.  Gradient
+ * accumulation (`--update_freq`, run_pretraining.py:42,375) under ZeRO-1: the fp32 shard is the accumulator, the first micro-step of a cycle
+ * overwrites it (accumulate = 0: `out` is not read, the result is that of ivh_shard_sum_bf16 bit for bit), the later ones add to it. */
+int ivh_shard_sum_bf16_acc(const uint16_t* in, int W, int64_t chunk, float* out, int accumulate, void* stream);
+/* acc_f32[i] += float(grad[i]), grad bf16 (grad_is_bf16) or fp32, any n > 0 (n % 8 elements go one by one); both buffers 16-byte aligned.
+ * Adds one micro-step's flat gradient buffer to an fp32 accumulator; widening bf16 is exact, the sum is torch's `acc.add_(grad)` bit for bit. */
+int ivh_grad_accumulate(const void* grad, int grad_is_bf16, float* acc_f32, int64_t n, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Stage-2 video-text contrastive logits + symmetric soft-target cross entropy

@@ -149,10 +149,17 @@ __global__ void clip_coef_kernel(const float* sumsq, float max_norm, float* coef
 
 // out[i] = sum_r float(in[r * chunk + i]), r ascending: the fp32 accumulation of the W bf16 gradient chunks one rank receives from an
 // all-to-all (the reduce half of a reduce-scatter whose wire format is bf16 but whose sum is exact in fp32).  W = 1: bf16 -> fp32.
+// ACC: the sum starts from out[i] instead of 0 (micro-steps 2.. of a gradient-accumulation cycle under ZeRO-1: the shard is the
+// accumulator); !ACC never reads `out`.
+template <bool ACC>
 __global__ __launch_bounds__(256) void shard_sum_kernel(const bf16_t* __restrict__ in, int W, long chunk, float* __restrict__ out) {
   const long nv = chunk >> 3;
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nv; i += (long)gridDim.x * 256) {
     float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if constexpr (ACC) {
+      const f32x4 a = reinterpret_cast<const f32x4*>(out)[2 * i], b = reinterpret_cast<const f32x4*>(out)[2 * i + 1];
+      acc[0] = a[0]; acc[1] = a[1]; acc[2] = a[2]; acc[3] = a[3]; acc[4] = b[0]; acc[5] = b[1]; acc[6] = b[2]; acc[7] = b[3];
+    }
     for (int r = 0; r < W; ++r) {
       float f[8];
       unpack8(reinterpret_cast<const u32x4*>(in + (long)r * chunk)[i], f);
@@ -164,18 +171,66 @@ __global__ __launch_bounds__(256) void shard_sum_kernel(const bf16_t* __restrict
   }
 }
 
+// acc[i] += float(grad[i]): one micro-step's flat gradient buffer (bf16 matrices / fp32 vectors) added to an fp32 accumulator.  8 elements
+// per thread and trip (one 16-byte load of bf16 or two of fp32, two 16-byte loads and stores of the accumulator); the last n % 8 elements
+// one by one.  Widening bf16 is exact, so this is torch's `acc.add_(grad)` bit for bit.
+template <bool BF16>
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const void* __restrict__ grad, float* __restrict__ acc, long n) {
+  const long nv = n >> 3;
+  const long stride = (long)gridDim.x * 256;
+  const long t0 = (long)blockIdx.x * 256 + threadIdx.x;
+  for (long i = t0; i < nv; i += stride) {
+    float g[8];
+    if constexpr (BF16) {
+      unpack8(reinterpret_cast<const u32x4*>(grad)[i], g);
+    } else {
+      const f32x4 x = reinterpret_cast<const f32x4*>(grad)[2 * i], y = reinterpret_cast<const f32x4*>(grad)[2 * i + 1];
+      g[0] = x[0]; g[1] = x[1]; g[2] = x[2]; g[3] = x[3]; g[4] = y[0]; g[5] = y[1]; g[6] = y[2]; g[7] = y[3];
+    }
+    f32x4 a = reinterpret_cast<f32x4*>(acc)[2 * i], b = reinterpret_cast<f32x4*>(acc)[2 * i + 1];
+    a[0] += g[0]; a[1] += g[1]; a[2] += g[2]; a[3] += g[3];
+    b[0] += g[4]; b[1] += g[5]; b[2] += g[6]; b[3] += g[7];
+    reinterpret_cast<f32x4*>(acc)[2 * i] = a;
+    reinterpret_cast<f32x4*>(acc)[2 * i + 1] = b;
+  }
+  const long j = (nv << 3) + t0;                           // tail: fewer than 8 elements, the first threads of the grid
+  if (j < n) {
+    if constexpr (BF16) acc[j] += __uint_as_float((unsigned)reinterpret_cast<const bf16_t*>(grad)[j] << 16);
+    else acc[j] += reinterpret_cast<const float*>(grad)[j];
+  }
+}
+
 }  // namespace ivh
 
 using namespace ivh;
 constexpr int SQNORM_BLOCKS = 1024;
 
-extern "C" int ivh_shard_sum_bf16(const uint16_t* in, int W, int64_t chunk, float* out, void* stream) {
+static int shard_sum_launch(const uint16_t* in, int W, int64_t chunk, float* out, bool accumulate, void* stream, const char* what) {
   IVH_REQUIRE(in && out && W >= 1 && chunk > 0 && chunk % 8 == 0, "shard_sum_bf16: bad args (chunk must be a multiple of 8)");
   IVH_REQUIRE(((uintptr_t)in % 16) == 0 && ((uintptr_t)out % 16) == 0, "shard_sum_bf16: buffers must be 16-byte aligned");
   long blocks = (chunk / 8 + 255) / 256;
   if (blocks > 4096) blocks = 4096;
-  hipLaunchKernelGGL(shard_sum_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, W, (long)chunk, out);
-  return ivh_host::check_launch("shard_sum_bf16");
+  if (accumulate) hipLaunchKernelGGL(shard_sum_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, W, (long)chunk, out);
+  else hipLaunchKernelGGL(shard_sum_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, in, W, (long)chunk, out);
+  return ivh_host::check_launch(what);
+}
+
+extern "C" int ivh_shard_sum_bf16(const uint16_t* in, int W, int64_t chunk, float* out, void* stream) {
+  return shard_sum_launch(in, W, chunk, out, false, stream, "shard_sum_bf16");
+}
+
+extern "C" int ivh_shard_sum_bf16_acc(const uint16_t* in, int W, int64_t chunk, float* out, int accumulate, void* stream) {
+  return shard_sum_launch(in, W, chunk, out, accumulate != 0, stream, "shard_sum_bf16_acc");
+}
+
+extern "C" int ivh_grad_accumulate(const void* grad, int grad_is_bf16, float* acc_f32, int64_t n, void* stream) {
+  IVH_REQUIRE(grad && acc_f32 && n > 0, "grad_accumulate: bad args");
+  IVH_REQUIRE(((uintptr_t)grad % 16) == 0 && ((uintptr_t)acc_f32 % 16) == 0, "grad_accumulate: buffers must be 16-byte aligned");
+  long blocks = ((n + 7) / 8 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  if (grad_is_bf16) hipLaunchKernelGGL(grad_accumulate_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, acc_f32, (long)n);
+  else hipLaunchKernelGGL(grad_accumulate_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, grad, acc_f32, (long)n);
+  return ivh_host::check_launch("grad_accumulate");
 }
 
 static int adamw_launch(float* master, float* exp_avg, float* exp_avg_sq, const void* grad, int grad_bf16, uint16_t* shadow_bf16, int64_t n,

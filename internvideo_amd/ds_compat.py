@@ -80,14 +80,15 @@ class IVDeepSpeedEngine:
         """gradient_accumulation_steps > 1 (`--update_freq`, run_pretraining.py:42,375; deepspeed==0.10.1 runtime/engine.py: backward scales the
         loss by 1 / gas, step() only acts when micro_steps is a multiple of gas and zeroes the gradients there): every micro-step's gradients are
         added to fp32 accumulators (IVTrainEngine.accumulate), the ranks' sums meet at the boundary, then clip + AdamW with the schedule values
-        the loop wrote for THAT iteration."""
+        the loop wrote for THAT iteration.  With reduce_mode='zero1' (`--zero_stage 1`) every micro-step is reduced as it runs, overlapped with
+        its backward, into the fp32 shard that is the accumulator; the boundary issues no gradient collective."""
         if int(gradient_accumulation_steps) < 1:
             raise ValueError(f"gradient_accumulation_steps = {gradient_accumulation_steps}")
         if engine_cls is None:
             from .engine import IVTrainEngine as engine_cls        # noqa: N813
         self.module = module
-        if int(gradient_accumulation_steps) > 1:
-            engine_kw.setdefault("overlap", False)               # nothing goes to the wire before the boundary
+        if int(gradient_accumulation_steps) > 1 and engine_kw.get("reduce_mode", "allreduce") != "zero1":
+            engine_kw.setdefault("overlap", False)               # replicated modes: nothing goes to the wire before the boundary
         if model_parameters is None:                           # optim_factory.get_parameter_groups (:56-98) without layer decay
             skip = set(module.no_weight_decay()) if hasattr(module, "no_weight_decay") else set()
             decay, no_decay = [], []
@@ -181,6 +182,10 @@ class IVDeepSpeedEngine:
 
     # ---- checkpoints (utils.py:500-519 save_model, :688-700 load_specific_model) -------------------------------------------------
     def save_checkpoint(self, save_dir, tag=None, client_state=None, save_latest=True):
+        if getattr(self.engine, "_acc_n", 0) > 0:
+            raise RuntimeError("IVDeepSpeedEngine.save_checkpoint in the middle of a gradient-accumulation cycle "
+                               f"({self.engine._acc_n} of {self._gas} micro-steps accumulated): the accumulators are not part of a checkpoint; "
+                               "save at a boundary")
         tag = tag or f"global_step{self.global_steps}"
         path = os.path.join(save_dir, str(tag))
         if hasattr(self.engine, "consolidate"):

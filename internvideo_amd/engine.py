@@ -25,6 +25,12 @@ design sized for 288 GB of HBM per GPU:
                             links, no ring), the W received pieces are accumulated in fp32 by `ivh_shard_sum_bf16` (exact fp32
                             sum, bf16 on the wire), AdamW updates only this rank's 1/W of master / moments / bf16 copy, and one
                             all-gather per bucket redistributes the bf16 compute copy.  AdamW streams 28 B x params / W.
+                            Gradient accumulation (`--update_freq`): the shard IS the accumulator.  Every micro-step sends its bf16
+                            buckets through the same all-to-all, overlapped with backward as in a plain step, and
+                            `ivh_shard_sum_bf16_acc` adds the W pieces onto `grad_shard32` (the first micro-step of a cycle overwrites
+                            it); no full-size fp32 accumulator exists and nothing is left to reduce at the boundary.  Wire bytes per
+                            optimizer step: gas x a bf16 all-to-all -- for gas = 2 the bytes of one fp32 reduce-scatter at the
+                            boundary, but hidden behind backward.  Neither form has been measured on more than one GPU.
   * the weight-decay split follows optim_factory.get_parameter_groups (:56-98): 1-D params, *.bias and the
     no_weight_decay() names are not decayed -- which is exactly the fp32 "vector" region -- so one fused AdamW launch
     per region (per bucket shard in zero1 mode) updates master, moments and the bf16 copy.
@@ -267,6 +273,9 @@ class IVTrainEngine:
         self.grad_norm = torch.zeros(1, dtype=F32, device=dev)
         self.reduce_log: List[Tuple[int, int]] = []
         self._defer_reduce = False
+        self._capture_comm = False                             # the captured graph contains its collectives (capture_comm=True)
+        self._acc_mat = self._acc_vec = None                   # gradient accumulation: see accumulate()
+        self._acc_n = 0                                        # micro-steps accumulated since the last optimizer step
         self._seg_capture = None                               # live state of a segmented capture (capture_step(segmented=True))
         self._segments = None                                  # [(graph, [(lo, hi)], reduce the vector region too)] in replay order
         self.comm_stream = torch.cuda.Stream(device=dev) if (self.comm and dev.type == "cuda") else None
@@ -325,9 +334,12 @@ class IVTrainEngine:
             recv = self.a2a_recv[lo:hi]
             dist.all_to_all_single(recv, g, group=self.pg)     # piece r of every rank's bucket lands on rank r
             out = self.grad_shard32[lo // self.world:hi // self.world]
+            acc = self._acc_n > 0                              # micro-steps 2.. of an accumulation cycle add to the shard; a plain step overwrites
             if recv.is_cuda:
-                ops.shard_sum_bf16(recv, self.world, out)
-            else:                                              # host tensors only occur in the gloo tests of the reduction logic
+                ops.shard_sum_bf16_acc(recv, self.world, out, acc)
+            elif acc:                                          # host tensors only occur in the gloo tests of the reduction logic
+                out.add_(torch.sum(recv.view(self.world, -1), dim=0, dtype=F32))
+            else:
                 torch.sum(recv.view(self.world, -1), dim=0, dtype=F32, out=out)
         elif self.grad_comm32 is not None:
             c32 = self.grad_comm32[lo:hi]
@@ -417,27 +429,87 @@ class IVTrainEngine:
         self._reduce_vec()
 
     # ---- gradient accumulation (run_pretraining.py:42,375 `--update_freq` = DeepSpeed's gradient_accumulation_steps) ------------------------
+    def _accumulate_into(self, grad: torch.Tensor, acc: torch.Tensor):
+        if acc.is_cuda:
+            ops.grad_accumulate(grad, acc)
+        else:                                                  # host tensors only occur in the gloo tests of the reduction logic
+            acc.add_(grad)
+
+    def _accumulate_reduced_vec(self):
+        """zero1: close a micro-step whose reduction has finished (the shard sums are in `grad_shard32`, `grad_vec` is all-reduced)"""
+        if self._acc_vec is None:
+            self._acc_vec = torch.zeros(self.n_vec, dtype=F32, device=self.device)
+        self._accumulate_into(self.grad_vec, self._acc_vec)
+        self._acc_n += 1
+
     def accumulate(self):
-        """add the gradients of the micro-step that just ran its backward (flat bf16 matrix buffer, fp32 vector buffer: both are rewritten by
-        every backward) to fp32 accumulators; nothing is reduced over the ranks until the boundary (optimizer_step(accumulated=True))."""
+        """add the gradients of the micro-step that just ran its backward to the accumulators of the cycle; optimizer_step(accumulated=True)
+        ends the cycle.
+          replicated modes: the flat bf16 matrix buffer and the fp32 vector buffer (both rewritten by every backward) are added to full-size
+                            fp32 accumulators; nothing is reduced over the ranks until the boundary.
+          zero1:            the accumulator of the matrix region is `grad_shard32`: the micro-step's reduction is finished here (remaining
+                            buckets, the vector region's all-reduce, the join with the communication stream) and its shard sums have been
+                            added onto the shard by _reduce_bucket; the reduced vector region is added to `_acc_vec`.  `_acc_mat` stays None."""
         from . import functional as Fn
+        if self._capture_comm:
+            raise RuntimeError("IVTrainEngine.accumulate(): the captured graph contains its collectives (capture_step(capture_comm=True)) and "
+                               "whether a shard sum overwrites or accumulates is a host-side launch argument frozen into it; capture with "
+                               "segmented=True or defer_reduce=True")
         if self.zero1:
-            raise NotImplementedError("IVTrainEngine: gradient accumulation with reduce_mode='zero1' is not built")
+            self._finish_reduce()                              # flushes queued weight gradients, launches what the hooks have not
+            if self._defer_reduce:
+                self.reduce_all_now()
+            self._accumulate_reduced_vec()
+            return
+        if self.comm and self._next_bucket != 0:
+            raise RuntimeError("IVTrainEngine.accumulate(): a bucket of this micro-step has already been reduced over the ranks (overlap=True "
+                               "hooks or _finish_reduce ran); the boundary's all-reduce would count it `world` times.  Build the engine "
+                               "with overlap=False for gradient accumulation in the replicated modes")
         Fn._wgrad_flush(force=True)                            # weight gradients still queued for a grouped launch
         if self.wgrad_stream is not None:
             torch.cuda.current_stream().wait_stream(self.wgrad_stream)
-        if getattr(self, "_acc_mat", None) is None:
+        if self._acc_mat is None:
             self._acc_mat = torch.zeros(self.n_mat, dtype=F32, device=self.device)
             self._acc_vec = torch.zeros(self.n_vec, dtype=F32, device=self.device)
-            self._acc_n = 0
-        self._acc_mat.add_(self.grad_mat)
-        self._acc_vec.add_(self.grad_vec)
+        self._accumulate_into(self.grad_mat, self._acc_mat)
+        self._accumulate_into(self.grad_vec, self._acc_vec)
         self._acc_n += 1
 
+    def replay_micro_step(self):
+        """replay the captured step (capture_step(defer_reduce=True) or segmented=True: the collectives are eager) on the current contents of
+        the static inputs as ONE micro-step of an accumulation cycle: accumulate(), no optimizer.  -> (loss, parts) device scalars.  The
+        captured loss is not divided by the number of micro-steps: end the cycle with optimizer_step(accumulated=True, average=True)."""
+        if self._capture_comm:
+            raise RuntimeError("IVTrainEngine.replay_micro_step(): the captured graph contains its collectives (capture_comm=True)")
+        if self._segments is None and getattr(self, "_graph", None) is None:
+            raise RuntimeError("IVTrainEngine.replay_micro_step() without a captured step")
+        if self._segments is not None:
+            self._replay_segments()                            # every bucket and the vector region are reduced between the segments
+        else:
+            self._graph.replay()
+        if self.check_finite:
+            self._guard_finite(self._graph_out[0])
+        if self.zero1 and self._segments is not None:
+            self._accumulate_reduced_vec()                     # (accumulate() would finish a reduction that is already complete)
+        else:
+            self.accumulate()                                  # replicated + segments: refused there, the buckets have been reduced
+        return self._graph_out
+
     # ---- optimizer ------------------------------------------------------------------------------------------------------
-    def optimizer_step(self, lr: Optional[float] = None, weight_decay: Optional[float] = None, accumulated: bool = False):
-        """accumulated=True: the step of a gradient-accumulation boundary -- the fp32 sums of accumulate() are all-reduced over the ranks
-        (one exact fp32 sum per region, no overlap) and take the place of this micro-step's buffers; they are zeroed afterwards."""
+    def optimizer_step(self, lr: Optional[float] = None, weight_decay: Optional[float] = None, accumulated: bool = False,
+                       average: bool = False):
+        """accumulated=True: the step of a gradient-accumulation boundary on the sums of accumulate(), which are cleared afterwards.
+        Replicated modes: the fp32 sums are all-reduced over the ranks here (one exact fp32 sum per region, no overlap).  zero1: every
+        micro-step was reduced as it ran, so NO gradient collective is issued: `grad_shard32` and `_acc_vec` are the gradients.
+        average=True (with accumulated): the sums are divided by the number of micro-steps -- folded into AdamW's gradient scale and the clip
+        threshold -- for micro-steps whose loss was not divided by it (replay_micro_step: a captured loss cannot be)."""
+        if self._acc_n > 0 and not accumulated:
+            raise RuntimeError(f"IVTrainEngine.optimizer_step(): {self._acc_n} micro-step(s) are accumulated; end the cycle with "
+                               "optimizer_step(accumulated=True)")
+        if average and not accumulated:
+            raise ValueError("IVTrainEngine.optimizer_step(average=True) needs accumulated=True")
+        if accumulated and (self._acc_n == 0 or (self._acc_mat is None and not self.zero1)):
+            raise RuntimeError("IVTrainEngine.optimizer_step(accumulated=True) without a preceding accumulate()")
         lr = self.lr if lr is None else lr
         wd = self.weight_decay if weight_decay is None else weight_decay
         self.step_count += 1
@@ -446,13 +518,18 @@ class IVTrainEngine:
         n_mat, W = self.n_mat, self.world
         mat_grad = self.grad_comm32 if self.grad_comm32 is not None else self.grad_mat
         vec_grad = self.grad_vec
+        norm_div = float(W)                                    # the buffers hold SUMS over the ranks (and, averaged, over the micro-steps)
         if accumulated:
-            if getattr(self, "_acc_mat", None) is None or self._acc_n == 0:
-                raise RuntimeError("IVTrainEngine.optimizer_step(accumulated=True) without a preceding accumulate()")
-            if self.comm:
-                dist.all_reduce(self._acc_mat, group=self.pg)
-                dist.all_reduce(self._acc_vec, group=self.pg)
-            mat_grad, vec_grad = self._acc_mat, self._acc_vec
+            if self.zero1:
+                vec_grad = self._acc_vec                       # reduced micro-step by micro-step; the matrix region is grad_shard32
+            else:
+                if self.comm:
+                    dist.all_reduce(self._acc_mat, group=self.pg)
+                    dist.all_reduce(self._acc_vec, group=self.pg)
+                mat_grad, vec_grad = self._acc_mat, self._acc_vec
+            if average:
+                gs /= self._acc_n
+                norm_div *= self._acc_n
         if self.max_grad_norm and self.max_grad_norm > 0:
             if self.zero1:                                     # shard norms meet in one scalar all-reduce; the vector region is replicated
                 ops.sqnorm(self.grad_shard32, self._sumsq, False, self._sq_scratch)
@@ -460,8 +537,8 @@ class IVTrainEngine:
             else:
                 ops.sqnorm(mat_grad, self._sumsq, False, self._sq_scratch)
             ops.sqnorm(vec_grad, self._sumsq, True, self._sq_scratch)
-            clip, nrm = ops.clip_coef(self._sumsq, self.max_grad_norm * W)
-            self.grad_norm = nrm / W
+            clip, nrm = ops.clip_coef(self._sumsq, self.max_grad_norm * norm_div)
+            self.grad_norm = nrm / norm_div
         b1, b2 = self.betas
         if self.zero1:
             for lo, hi in self.buckets:
@@ -483,7 +560,9 @@ class IVTrainEngine:
         ops.adamw_step(self.master[n_mat:], self.exp_avg[n_mat:], self.exp_avg_sq[n_mat:], vec_grad, None,
                        lr, b1, b2, self.eps, 0.0, self.step_count, gs, clip, lr_segments=self._lr_seg_vec)
         if accumulated:
-            self._acc_mat.zero_(); self._acc_vec.zero_()
+            if self._acc_mat is not None:
+                self._acc_mat.zero_()
+            self._acc_vec.zero_()                              # (zero1: the next cycle's first micro-step overwrites grad_shard32)
             self._acc_n = 0
         if self.zero1 and self.comm_stream is not None:
             torch.cuda.current_stream().wait_stream(self.comm_stream)
@@ -571,6 +650,7 @@ class IVTrainEngine:
         segmented = bool(self.comm and segmented and not capture_comm)
         self._segments = None
         self._defer_reduce = bool(self.comm and defer_reduce and not capture_comm and not segmented)
+        self._capture_comm = bool(self.comm and capture_comm)
         self.tower.grad_ready_hook = self._block_hook() if (self.overlap and not self._defer_reduce) else None
 
         def body():

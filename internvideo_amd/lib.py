@@ -135,6 +135,8 @@ SIGNATURES = {
     "ivh_sqnorm": [_vp, _i32, _i64, _vp, _vp, _i32, _vp],
     "ivh_clip_coef": [_vp, _f32, _vp, _vp, _vp],
     "ivh_shard_sum_bf16": [_vp, _i32, _i64, _vp, _vp],
+    "ivh_shard_sum_bf16_acc": [_vp, _i32, _i64, _vp, _i32, _vp],
+    "ivh_grad_accumulate": [_vp, _i32, _vp, _i64, _vp],
     "ivh_vtc_workspace_floats": [_i32, _i32],
     "ivh_vtc_abt": [_vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp],
     "ivh_vtc_loss_fwd_bwd": [_vp, _vp, _vp, _i32, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -1175,6 +1175,26 @@ def shard_sum_bf16(recv: torch.Tensor, W: int, out: torch.Tensor) -> None:
     call("ivh_shard_sum_bf16", ptr(recv), int(W), chunk, ptr(out), stream_ptr())
 
 
+def shard_sum_bf16_acc(recv: torch.Tensor, W: int, out: torch.Tensor, accumulate: bool) -> None:
+    """shard_sum_bf16 on top of what `out` holds: out = (out if accumulate else 0) + the W chunks in rank order.  accumulate=False does not
+    read `out` and gives shard_sum_bf16's bits."""
+    _L.require_gpu()
+    _chk(recv, BF16, "recv"); _chk(out, F32, "out")
+    chunk = recv.numel() // W
+    if recv.numel() != W * chunk or out.numel() != chunk:
+        raise InternVideoHipError("shard_sum_bf16_acc: recv must hold W chunks of out.numel() elements")
+    call("ivh_shard_sum_bf16_acc", ptr(recv), int(W), chunk, ptr(out), int(bool(accumulate)), stream_ptr())
+
+
+def grad_accumulate(grad: torch.Tensor, acc: torch.Tensor) -> None:
+    """acc fp32 [n] += grad (bf16 | fp32 [n]): a micro-step's flat gradient buffer into its fp32 accumulator"""
+    _L.require_gpu()
+    _chk(acc, F32, "acc")
+    if grad.dtype not in (BF16, F32) or not grad.is_contiguous() or grad.numel() != acc.numel() or grad.device != acc.device:
+        raise InternVideoHipError("grad_accumulate: grad must be a contiguous bf16 / fp32 buffer of acc.numel() elements on acc's device")
+    call("ivh_grad_accumulate", ptr(grad), int(grad.dtype == BF16), ptr(acc), acc.numel(), stream_ptr())
+
+
 # ---- stage-2 contrastive ------------------------------------------------------------------------------------------------
 def vtc_loss_fwd_bwd(v: torch.Tensor, t: torch.Tensor, idx: Optional[torch.Tensor], temp, want_grad: bool = True):
     """v, t fp32 [n,C] (already gathered over ranks), idx int64 [n] | None -> (loss[1], sim[n,n], dv, dt, dtemp[1]).
