@@ -57,12 +57,16 @@ typedef struct ivh_gemm_desc {
   int32_t act;                              /* 0 none, 1 GELU(erf), 2 GELU(tanh), 3 GELU(erf) with the DERIVATIVE exchanged:
                                                forward: `preact` receives gelu'(pre-activation) instead of the pre-activation
                                                (it falls out of the erf evaluation); backward: C *= dact_in as it is.  Saves
-                                               the 128 erf + exp per lane and tile of the fc2 dgrad epilogue. */
+                                               the 128 erf + exp per lane and tile of the fc2 dgrad epilogue.
+                                               4 GELU(tanh) with the derivative exchanged, the twin of 3: forward C = gelu_tanh(..),
+                                               `preact` receives gelu_tanh'(pre-activation) (value and derivative share one exp and
+                                               one reciprocal); backward: C *= dact_in as it is (the code path of 3, colsum_part
+                                               included).  Accepted wherever 3 is; 2 keeps the pre-activation copy and recomputes. */
   uint16_t* preact; int64_t ldp;            /* optional bf16 [M][N] copy of the pre-activation */
   const uint16_t* dact_in; int64_t ldd;     /* optional bf16 [M][N]: C *= act'(dact_in) (act selects the flavour) */
   float alpha;
   int32_t batch;
-  float* colsum_part;                       /* optional fp32 [2 * ceil(M / 256)][N] (256^2 kernel, dact_in launches with act = 3 only): row block
+  float* colsum_part;                       /* optional fp32 [2 * ceil(M / 256)][N] (256^2 kernel, dact_in launches with act = 3 / 4 only): row block
                                                sums of C over m, i.e. the bias gradient of the layer whose dgrad this is, as a
                                                by-product of the epilogue; reduce with ivh_colsum_finish.  NULL = not wanted. */
   int64_t strideA, strideB, strideC, stride_bias, stride_preact, stride_dact;
@@ -76,7 +80,7 @@ typedef struct ivh_gemm_desc {
    *   m_dev: int32 in HBM, 0 <= *m_dev <= M: rows of A / C / preact / dact_in (a_kc = 1: forward and dgrad launches);
    *   k_dev: int32 in HBM, 0 <= *k_dev <= K: contraction length of a weight gradient (a_kc = b_kc = 0, plain epilogue); per problem in
    *          ivh_gemm_grouped_bf16.  *k_dev = 0 writes C = 0.
-   * 256x256 kernel only (bf16 output, batch 1, act 0 / 1-forward / 3); anything else is rejected.  colsum_part then holds
+   * 256x256 kernel only (bf16 output, batch 1, act 0 / 1-forward / 3 / 4); anything else is rejected.  colsum_part then holds
    * 2 * ceil(*m_dev / 256) valid rows: reduce with ivh_colsum_finish_dyn.  NULL (zero-initialised descriptors) = M / K as given. */
   const int32_t* m_dev; const int32_t* k_dev;
 } ivh_gemm_desc;
@@ -96,7 +100,7 @@ int ivh_gemm_grouped_bf16(const ivh_gemm_desc* d, int n, void* stream);
  * dequantisation multiplier, left in device memory), q = rne(x / scale).  amax_scratch: 4 bytes of device scratch.
  * ivh_gemm_fp8: C = epilogue(alpha * scale_a[0] * scale_b[0] * sum_k A(m,k) B(n,k)) with A, B = e4m3 bytes (d->A / d->B carry the byte
  * pointers, lda / ldb in bytes), both K-contiguous (a_kc = b_kc = 1: dgrad / wgrad use the transposed copies), fp32 accumulate on
- * v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, epilogues as ivh_gemm_bf16 (bias, act 0..3, preact, dact_in; no batch,
+ * v_mfma_scale_f32_16x16x128_f8f6f4 with unit block scales, epilogues as ivh_gemm_bf16 (bias, act 0..4, preact, dact_in; no batch,
  * no colsum_part).  K, lda, ldb multiples of 16. */
 int ivh_fp8_quantize(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
                      float* scale_out, uint32_t* amax_scratch, void* stream);
@@ -122,15 +126,15 @@ int ivh_gemm_fp8(const ivh_gemm_desc* d, const float* scale_a, const float* scal
  * ivh_gemm_fp8 / ivh_gemm_fp8_cs with d->m_dev or d->k_dev: always the 256x256 e4m3 kernel, whatever the size (the size test of a plain
  * launch, M * N >= 512^2 and K >= 512, is a speed heuristic; the kernel's K loop runs any K >= 1, so there is no structural K floor)
  * and whatever ivh_set_gemm_fp8_kernel says.
- *   m_dev: forward plain (+ bias), forward act = 1 / 3 (GELU; act = 3 with the gelu' copy in `preact`), dgrad plain, dgrad x dact_in
- *          (act = 3).  Same contract as the bf16 kernels: workgroups without a tile leave at once, descriptors end at the last kept
+ *   m_dev: forward plain (+ bias), forward act = 1 / 3 / 4 (GELU; act = 3 / 4 with the gelu' copy in `preact`), dgrad plain, dgrad x dact_in
+ *          (act = 3 / 4).  Same contract as the bf16 kernels: workgroups without a tile leave at once, descriptors end at the last kept
  *          row, rows behind the count are neither read nor written.  The x dact_in launch also accepts colsum_part (fp32
  *          [2 * ceil(M / 256)][N], as in ivh_gemm_desc): the bias gradient of the layer in front; reduce with ivh_colsum_finish_dyn.
  *   k_dev: the weight gradient dY^T x X^T on the transposed copies, contraction over the first *k_dev token columns (plain epilogue, no
  *          bias).  Both operands must hold zeros from column *k_dev up to the next multiple of 16 (ivh_fp8_quantize*_dyn writes them);
  *          nothing from there on is read.  *k_dev = 0 writes C = 0.
  * Rejected with an error (never handed to the 128x128 kernel, which would walk the stale rows): fp32 output, act = 2, batch > 1, a
- * pre-activation copy without act = 3, both counts at once, operands or outputs of 2 GiB or more.  No tail split:
+ * pre-activation copy without act = 3 / 4, both counts at once, operands or outputs of 2 GiB or more.  No tail split:
  * ivh_gemm_fp8_split_workspace answers 0 for such a descriptor. */
 int ivh_fp8_quantize_dyn(const uint16_t* x, int64_t ld, int M, int K, uint8_t* q, int64_t ldq, uint8_t* qt, int64_t ldt,
                          float* scale_out, uint32_t* amax_scratch, const int32_t* m_dev, void* stream);

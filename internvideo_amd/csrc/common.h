@@ -95,6 +95,20 @@ __device__ __forceinline__ float dgelu_tanh(float x) {
   const float du = 0.7978845608028654f * (1.0f + 3.0f * 0.044715f * x * x);
   return 0.5f * (1.0f + t) + 0.5f * x * (1.0f - t * t) * du;
 }
+// gelu_tanh(x) and gelu_tanh'(x) from ONE exp and one reciprocal (act = 4, every GEMM kernel: they agree up to accumulation order).
+// With u = c (x + a x^3):  s = (1 + tanh u) / 2 = 1 / (1 + exp(-2u)),  1 - tanh^2 u = 4 s (1 - s), so
+//   g = x s,   d = s + x s (1 - s) * 2c (1 + 3a x^2).
+// Saturation is exact and finite while x * x is finite in fp32 (|x| < 1.8e19; the GEMM epilogues see bf16-range pre-activations of a few
+// tens; beyond that d is NaN through 0 * inf, as in dgelu_tanh): exp(-2u) = +inf gives s = 0 (g = -0, d = 0), exp(-2u) = 0 gives s = 1 (g = x, d = 1); 1 - s is
+// taken from the same rounded s, so s (1 - s) is never negative.  A caller that drops d pays for g alone.
+__device__ __forceinline__ void gelu_tanh_pair(float x, float& g, float& d) {
+  const float x2 = x * x;
+  const float u2 = (-2.0f * 0.7978845608028654f) * x * fmaf(0.044715f, x2, 1.0f);       // -2u
+  const float s = __builtin_amdgcn_rcpf(1.0f + __expf(u2));
+  g = x * s;
+  const float du2 = fmaf(2.0f * 0.7978845608028654f * 3.0f * 0.044715f, x2, 2.0f * 0.7978845608028654f);   // 2c (1 + 3a x^2)
+  d = fmaf(g * (1.0f - s), du2, s);
+}
 
 // Counter-based dropout mask: keep(element) = hash(seed, 64-bit element index) >= p * 2^32.  Stateless, so forward and backward kernels
 // (and a host-side check, tests/test_bert_gpu.py::dropout_keep_mask) regenerate the same mask from (seed, index) alone.

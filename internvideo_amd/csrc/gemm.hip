@@ -171,8 +171,14 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += bv[r];
       }
+      float tg[4], td[4];                                // act = 4: gelu_tanh and its derivative from one exp (common.h)
+      if (p.act == 4 && (preact || !dact)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gelu_tanh_pair(v[r], tg[r], td[r]);
+      }
       if (preact) {
-        if (p.act == 3) *reinterpret_cast<u32x2*>(preact + (long)m * p.ldp + n) = pack4(dgelu_erf(v[0]), dgelu_erf(v[1]), dgelu_erf(v[2]), dgelu_erf(v[3]));
+        if (p.act == 4) *reinterpret_cast<u32x2*>(preact + (long)m * p.ldp + n) = pack4(td[0], td[1], td[2], td[3]);
+        else if (p.act == 3) *reinterpret_cast<u32x2*>(preact + (long)m * p.ldp + n) = pack4(dgelu_erf(v[0]), dgelu_erf(v[1]), dgelu_erf(v[2]), dgelu_erf(v[3]));
         else *reinterpret_cast<u32x2*>(preact + (long)m * p.ldp + n) = pack4(v[0], v[1], v[2], v[3]);
       }
       if (dact) {
@@ -180,13 +186,16 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
         float u[4] = {__uint_as_float(uu[0] << 16), __uint_as_float(uu[0] & 0xffff0000u),
                       __uint_as_float(uu[1] << 16), __uint_as_float(uu[1] & 0xffff0000u)};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= (p.act == 3) ? u[r] : ((p.act == 2) ? dgelu_tanh(u[r]) : dgelu_erf(u[r]));
+        for (int r = 0; r < 4; ++r) v[r] *= (p.act == 3 || p.act == 4) ? u[r] : ((p.act == 2) ? dgelu_tanh(u[r]) : dgelu_erf(u[r]));
       } else if (p.act == 1 || p.act == 3) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
       } else if (p.act == 2) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+      } else if (p.act == 4) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = tg[r];
       }
       if (p.c_fp32) {
         float* C = reinterpret_cast<float*>(p.C) + (long)z * p.strideC;
@@ -276,11 +285,11 @@ extern "C" int ivh_gemm_bf16(const ivh_gemm_desc* d, void* stream) {
   if (d->b_kc) IVH_REQUIRE(d->K % 8 == 0, "gemm: K=%d must be a multiple of 8 for a K-contiguous B", d->K);
   IVH_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && ((uintptr_t)d->C % 16) == 0,
               "gemm: base pointers must be 16-byte aligned");
-  IVH_REQUIRE(d->act >= 0 && d->act <= 3, "gemm: unknown activation %d", d->act);
+  IVH_REQUIRE(d->act >= 0 && d->act <= 4, "gemm: unknown activation %d", d->act);
   IVH_REQUIRE(!d->colsum_part || ivh_gemm_select(d) == 2, "gemm: colsum_part is produced by the 256x256 dgrad epilogue only (check ivh_gemm_select)");
   if (d->m_dev || d->k_dev) {
     IVH_REQUIRE(ivh_gemm256_supported(d) && ivh_gemm256_fits(d) && (d->batch <= 1) && !d->c_fp32,
-                "gemm: device-side row counts (m_dev / k_dev) need the 256x256 kernel: bf16 output, batch 1, operands below 2 GiB, erf-GELU or plain epilogue");
+                "gemm: device-side row counts (m_dev / k_dev) need the 256x256 kernel: bf16 output, batch 1, operands below 2 GiB, plain epilogue, erf-GELU forward without a pre-activation copy (act = 1), or GELU with the derivative exchanged (act = 3 / 4)");
     IVH_REQUIRE(((uintptr_t)d->m_dev % 4) == 0 && ((uintptr_t)d->k_dev % 4) == 0, "gemm: m_dev / k_dev must be 4-byte aligned");
     return ivh_gemm256_launch(d, stream);
   }

@@ -263,8 +263,11 @@ __device__ __forceinline__ G2Tile g2_decode(int lin, int tiles_m, int tiles_n) {
 // before a counted vmcnt can see them.
 // EPI = 0: C = alpha * acc + bias;  EPI = 2: C = gelu_erf(alpha * acc + bias) with optional pre-activation copy;
 // EPI = 1: C = (alpha * acc + bias) * gelu_erf'(dact_in);  EPI = 3: C = (alpha * acc + bias) * dact_in (act = 3: the forward
-// stored the derivative).  With act = 3, EPI = 2 writes gelu'(pre-activation) into `preact`.  bf16 output only; tanh-GELU and
-// fp32 outputs use the 128^2 kernel.
+// stored the derivative).  With act = 3, EPI = 2 writes gelu'(pre-activation) into `preact`.
+// EPI = 4: the tanh twin of EPI = 2 (act = 4): C = gelu_tanh(alpha * acc + bias), `preact` receives gelu_tanh'(pre-activation)
+// (gelu_tanh_pair, common.h); its backward is EPI = 3 as it stands.  Built for every launch mode EPI = 2 has (plain, SPLIT, HALF, DYN,
+// DYN + SPLIT; e4m3: plain, SPLIT, DYN), so the kernel the router picks does not depend on the activation.
+// bf16 output only; fp32 outputs and act = 2 (tanh-GELU that keeps the pre-activation and recomputes the derivative) use the 128^2 kernel.
 // (One epilogue flavour per kernel: with all of them behind run-time flags the tile boundary was ~120 KB of code, and the
 // instruction-cache misses of hopping over the dead flavours cost more than the K loop of a 22-step tile.)
 // GROUPED: up to 32 independent problems (e.g. the weight-gradient GEMMs of three transformer blocks: 3 x (102 + 36 + 144 + 144)
@@ -974,7 +977,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
       asm volatile("" : "+v"(i16e), "+v"(g4e));          // opaque: nothing of the address math is hoisted across the K loop
       const int mrow = t.m0 + wm * 128 + i16e;           // + mt * 16
       const int ncol = t.n0 + wn * wcols + 4 * g4e;      // + nt * 16
-      const bool has_bias = p.bias != nullptr, has_pre = (EPI == 2) && p.preact != nullptr, live = p.debug_skip_stores == 0 && unit_live;
+      const bool has_bias = p.bias != nullptr, has_pre = (EPI == 2 || EPI == 4) && p.preact != nullptr, live = p.debug_skip_stores == 0 && unit_live;
       const unsigned b_lane = (unsigned)((t.z * p.stride_bias + ncol) * 4);
       if constexpr (FP8) {
         if (p.scale_b_vec) {                                // per-channel weight scales: the accumulators take their column's scale in place
@@ -1053,7 +1056,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
             }
         }
         // one pass = the 8 fragments of this tile pair -> LDS window -> 4 row-major stores.  MODE 0: alpha * acc + bias,
-        // 1: (..) * gelu'(u), 2: gelu(..).  The affine part is recomputed per pass instead of holding 32 floats across passes.
+        // 1: (..) * gelu'(u), 2: gelu(..), 4: gelu_tanh(..).  The affine part is recomputed per pass instead of holding 32 floats across passes.
         auto pass = [&](auto mode_c, bool last, const __amdgpu_buffer_rsrc_t& rs, unsigned lane_off, int ld) {
           constexpr int MODE = decltype(mode_c)::value;
 #pragma unroll
@@ -1077,16 +1080,20 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
               } else if constexpr (MODE == 2) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = g2_gelu(v[r]);
+              } else if constexpr (MODE == 4) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { float dv; gelu_tanh_pair(v[r], v[r], dv); }     // value alone: the derivative's share is dead code
               }
               const unsigned ch = (unsigned)(nt * 2 + (wcol >> 1)) ^ (unsigned)(wrow & 7);
               *reinterpret_cast<u32x2*>(win + w_off + mt2 * 2048 + (ch << 4)) = pack4(v[0], v[1], v[2], v[3]);
             }
           flush(rs, lane_off, ld, pr);
         };
-        if constexpr (EPI == 2) {
+        if constexpr (EPI == 2 || EPI == 4) {
           if (has_pre) {
-            // fc1 of the training step (act = 3; a pre-activation copy with act = 1 runs on the 128^2 kernel): gelu and gelu' share
-            // one erf / exp; the derivative goes through the window first while the packed activations wait in 16 VGPRs
+            // fc1 of the training step (act = 3 / 4; a pre-activation copy with act = 1 runs on the 128^2 kernel): gelu and gelu' share
+            // one erf / exp (EPI 4, tanh: one exp / rcp); the derivative goes through the window first while the packed activations
+            // wait in 16 VGPRs
             u32x2 gpk[2][4];
 #pragma unroll
             for (int mt2 = 0; mt2 < 2; ++mt2)
@@ -1095,7 +1102,10 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
                 const int mt = pr * 2 + mt2;
                 float gv[4], dv[4];
 #pragma unroll
-                for (int r = 0; r < 4; ++r) g2_gelu_pair(acc[mt][nt][r] * alpha + bv[nt][r], gv[r], dv[r]);
+                for (int r = 0; r < 4; ++r) {
+                  if constexpr (EPI == 4) gelu_tanh_pair(acc[mt][nt][r] * alpha + bv[nt][r], gv[r], dv[r]);
+                  else g2_gelu_pair(acc[mt][nt][r] * alpha + bv[nt][r], gv[r], dv[r]);
+                }
                 acc[mt][nt] = f32x4{zero1, zero1, zero1, zero1};
                 const unsigned ch = (unsigned)(nt * 2 + (wcol >> 1)) ^ (unsigned)(wrow & 7);
                 *reinterpret_cast<u32x2*>(win + w_off + mt2 * 2048 + (ch << 4)) = pack4(dv[0], dv[1], dv[2], dv[3]);
@@ -1111,7 +1121,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
               }
             flush(rs_ct, c_st, eldc, pr);
           } else {
-            pass(std::integral_constant<int, 2>{}, true, rs_ct, c_st, eldc);
+            pass(std::integral_constant<int, EPI>{}, true, rs_ct, c_st, eldc);
           }
         } else {
           pass(std::integral_constant<int, EPI>{}, true, rs_ct, c_st, eldc);
@@ -1153,6 +1163,11 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
 }  // namespace ivh
 
 // Launcher used by ivh_gemm_bf16 (gemm.hip) when the 256^2 kernel is selected.  Arguments were validated there.
+// The kernel's EPI flavour for a descriptor.  act = 3 / 4 (erf / tanh GELU with the derivative exchanged) share the x dact_in epilogue;
+// forward launches with act = 4 run the tanh twin (EPI 4) of the GELU epilogue (EPI 2), in every launch mode EPI 2 is built for.
+static inline bool g2_act_d(int act) { return act == 3 || act == 4; }
+static inline int g2_epi(const ivh_gemm_desc* d) { return d->dact_in ? (g2_act_d(d->act) ? 3 : 1) : (d->act == 4 ? 4 : (d->act ? 2 : 0)); }
+static inline bool g2_gelu_epi(int epi) { return epi == 2 || epi == 4; }
 static int g_g2_stagger = -1, g_g2_skip_stores = 0;      // -1 = choose per launch
 static unsigned long long* g_g2_stamps = nullptr;
 static int g_g2_max_wg = 0;                               // measurement aid: cap the number of workgroups (0 = #CUs)
@@ -1218,15 +1233,15 @@ extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8) {
     // sized for the largest plan a launch on `cap` workgroups can make (one 256 KiB slab per workgroup).  Long K only: a slice needs
     // nk - 2 * per >= 40 with per >= 2 loop trips.
     if (fp8) return 0;
-    const int epi_d = d->dact_in ? (d->act == 3 ? 3 : 1) : (d->act ? 2 : 0);
-    if (epi_d == 1 || (epi_d == 2 && !d->b_kc) || (epi_d == 3 && d->b_kc)) return 0;
+    const int epi_d = g2_epi(d);
+    if (epi_d == 1 || (g2_gelu_epi(epi_d) && !d->b_kc) || (epi_d == 3 && d->b_kc)) return 0;
     if ((d->K + 63) / 64 < 44) return 0;
     const long capd = g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu();
     return 4096 + (int64_t)capd * 262144;
   }
   if (fp8 && !d->b_kc) return 0;
-  const int epi = d->dact_in ? (d->act == 3 ? 3 : 1) : (d->act ? 2 : 0);
-  if (epi == 1 || (epi == 2 && !d->b_kc) || (epi == 3 && (fp8 ? false : d->b_kc))) return 0;
+  const int epi = g2_epi(d);
+  if (epi == 1 || (g2_gelu_epi(epi) && !d->b_kc) || (epi == 3 && (fp8 ? false : d->b_kc))) return 0;
   const long total = (long)((d->M + ivh::G2_BM - 1) / ivh::G2_BM) * ((d->N + ivh::G2_BN - 1) / ivh::G2_BN);
   const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu();
   const int bke = fp8 ? 128 : 64;
@@ -1308,8 +1323,8 @@ static int g_g2_half = [] { const char* e = getenv("IVH_NO_HALF"); return (e && 
 extern "C" int ivh_gemm256_debug_half(int mode) { g_g2_half = (mode >= 0 && mode <= 3) ? mode : 1; return 0; }   // 3 = interleaved by XCD block (A/B)
 static int g2_half_flavour(const ivh_gemm_desc* d) {     // the epilogue / layout combinations the HALF kernels are instantiated for
   if (!g_g2_half || !d->a_kc || d->c_fp32 || d->batch > 1 || d->m_dev || d->k_dev) return 0;
-  const int epi = d->dact_in ? (d->act == 3 ? 3 : 1) : (d->act ? 2 : 0);
-  return epi == 0 || (epi == 2 && d->b_kc) || (epi == 3 && !d->b_kc);
+  const int epi = g2_epi(d);
+  return epi == 0 || (g2_gelu_epi(epi) && d->b_kc) || (epi == 3 && !d->b_kc);
 }
 // host-side view of the plan ivh_gemm256_launch would use for `d` on `cap` workgroups (0 = the device's CUs):
 // out = {tiles_nf, half_begin, half_split, total_ids}; returns 1 when half-width tiles are used, else 0.
@@ -1328,10 +1343,10 @@ extern "C" double ivh_gemm256_half_rounds(const ivh_gemm_desc* d) {
 
 // The combinations the 256x256 kernel is built for (everything else runs on the 128x128 kernel of gemm.hip).
 extern "C" int ivh_gemm256_supported(const ivh_gemm_desc* d) {
-  if (d->c_fp32 || d->act == 2) return 0;
-  if (d->dact_in) return (d->act == 1 || d->act == 3) && d->a_kc && !d->b_kc && !d->preact;   // fc2 dgrad: dy W2 * gelu'(u)
+  if (d->c_fp32 || d->act == 2 || d->act < 0 || d->act > 4) return 0;           // (act = 2, tanh GELU with a pre-activation copy: 128^2 kernel)
+  if (d->dact_in) return (d->act == 1 || g2_act_d(d->act)) && d->a_kc && !d->b_kc && !d->preact;   // fc2 dgrad: dy W2 * gelu'(u)
   if (d->act == 1 && d->preact) return 0;                                         // u copy + erf GELU: 128^2 kernel
-  if (d->act == 1 || d->act == 3) return d->a_kc && d->b_kc;                     // fc1 forward: gelu(x W1^T + b) (+ gelu' copy)
+  if (d->act == 1 || g2_act_d(d->act)) return d->a_kc && d->b_kc;                // fc1 forward: gelu(x W1^T + b) (+ gelu' copy)
   return d->preact == nullptr;
 }
 
@@ -1369,7 +1384,7 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
   p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC; p.stride_bias = d->stride_bias;
   p.stride_preact = d->stride_preact; p.stride_dact = d->stride_dact;
   p.batch = nb; p.a_bytes = a_bytes; p.b_bytes = b_bytes;
-  p.colsum_part = (d->dact_in && d->act == 3 && nb == 1) ? d->colsum_part : nullptr;
+  p.colsum_part = (d->dact_in && g2_act_d(d->act) && nb == 1) ? d->colsum_part : nullptr;
   const long lim = (1L << 31) - (1L << 24);
   p.c_bytes = ((long)(nb - 1) * d->strideC + ((long)d->M - 1) * d->ldc + d->N) * (d->c_fp32 ? 4 : 2);
   p.p_bytes = d->preact ? ((long)(nb - 1) * d->stride_preact + ((long)d->M - 1) * d->ldp + d->N) * 2 : 0;
@@ -1392,14 +1407,14 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
   { const char* e = g_g2_stamps ? getenv("IVH_G2_STAMP_WG") : nullptr; p.debug_stamp_wg = e ? atoi(e) : 0; }
   const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
   hipStream_t s = (hipStream_t)stream;
-  const int epi = d->dact_in ? (d->act == 3 ? 3 : 1) : (d->act ? 2 : 0);
+  const int epi = g2_epi(d);
   p.m_dev = d->m_dev; p.k_dev = d->k_dev;
   if (d->m_dev || d->k_dev) {                             // device-side row counts (DYN kernels): no tail split, no half-width tiles
     IVH_REQUIRE(nb == 1 && !g_g2_dbg && !g_g2_sched, "gemm256: device-side row counts (m_dev / k_dev) are built for single, unbatched problems");
     IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm256: m_dev and k_dev are mutually exclusive");
     IVH_REQUIRE(!d->m_dev || d->a_kc, "gemm256: m_dev counts the rows of a K-contiguous A (forward / dgrad launches)");
     IVH_REQUIRE(!d->k_dev || (!d->a_kc && !d->b_kc && epi == 0), "gemm256: k_dev counts the rows of rows-contiguous operands (weight gradients, plain epilogue)");
-    IVH_REQUIRE(epi != 1, "gemm256: m_dev with the erf-recomputing dgrad epilogue (act = 1) is not built; use act = 3");
+    IVH_REQUIRE(epi != 1, "gemm256: m_dev with the erf-recomputing dgrad epilogue (act = 1) is not built; use act = 3 / 4");
     p.half_begin = p.total_tiles; p.half_split = 0; p.tiles_nf = p.tiles_n; p.half_interleave = 0;
     p.split_main = p.total_tiles; p.split_s = 0; p.split_nk2 = 0; p.split_ws = nullptr; p.split_cnt = nullptr; p.split_ws_bytes = 0;
     dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
@@ -1412,6 +1427,7 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
         if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
         else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
         else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
+        else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
         else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
         return ivh_host::check_launch("gemm256_bf16 (device-side row count, tail split)");
       }
@@ -1420,6 +1436,7 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
     else if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
     else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
     else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
+    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
     return ivh_host::check_launch("gemm256_bf16 (device-side row count)");
   }
@@ -1428,6 +1445,7 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
     if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, true>), grid, block, 0, s, p);
     else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, true>), grid, block, 0, s, p);
     else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, true>), grid, block, 0, s, p);
+    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, true>), grid, block, 0, s, p);
     return ivh_host::check_launch("gemm256_bf16 (tail split)");
   }
@@ -1440,6 +1458,7 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
       if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, false, true>), grid, block, 0, s, p);
       else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, false, true>), grid, block, 0, s, p);
       else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, false, true>), grid, block, 0, s, p);
+      else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, false, true>), grid, block, 0, s, p);
       else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, false, true>), grid, block, 0, s, p);
       return ivh_host::check_launch("gemm256_bf16 (half-width tiles)");
     }
@@ -1459,6 +1478,8 @@ extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
     else hipLaunchKernelGGL((gemm256_kernel<false, false, 0>), grid, block, 0, s, p);
   } else if (epi == 2) {
     hipLaunchKernelGGL((gemm256_kernel<true, true, 2>), grid, block, 0, s, p);
+  } else if (epi == 4) {
+    hipLaunchKernelGGL((gemm256_kernel<true, true, 4>), grid, block, 0, s, p);
   } else if (epi == 3) {
     hipLaunchKernelGGL((gemm256_kernel<true, false, 3>), grid, block, 0, s, p);
   } else {
@@ -1479,14 +1500,14 @@ extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale
   if (dyn) {
     IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm_fp8: m_dev and k_dev are mutually exclusive");
     IVH_REQUIRE(d->a_kc && d->b_kc && !d->c_fp32 && d->batch <= 1 && d->act != 2,
-                "gemm_fp8: device-side row counts need the 256x256 e4m3 kernel: K-contiguous operands, bf16 output, batch 1, erf-GELU or plain epilogue");
-    IVH_REQUIRE(!(d->dact_in && (d->act != 3 || d->preact)) && !(!d->dact_in && d->act != 3 && d->preact),
-                "gemm_fp8: device-side row counts: a pre-activation copy exists with act = 3 (GELU + gelu' copy) only, x gelu' with act = 3 only");
+                "gemm_fp8: device-side row counts need the 256x256 e4m3 kernel: K-contiguous operands, bf16 output, batch 1, plain, erf-GELU or derivative-exchanging (act = 3 / 4) epilogue");
+    IVH_REQUIRE(!(d->dact_in && (!g2_act_d(d->act) || d->preact)) && !(!d->dact_in && !g2_act_d(d->act) && d->preact),
+                "gemm_fp8: device-side row counts: a pre-activation copy exists with act = 3 / 4 (GELU + gelu' copy) only, x gelu' with act = 3 / 4 only");
     IVH_REQUIRE(!d->k_dev || (!d->dact_in && d->act == 0 && !d->bias && !d->preact), "gemm_fp8: k_dev counts the token rows of a weight gradient (plain epilogue, no bias)");
     IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in), "gemm_fp8: colsum_part is a by-product of the m_dev x gelu' dgrad launch");
   } else {
     if (!d->a_kc || !d->b_kc || d->c_fp32 || d->batch > 1 || d->colsum_part || d->act == 2) return 1;
-    if (d->dact_in && (d->act != 3 || d->preact)) return 1;
+    if (d->dact_in && (!g2_act_d(d->act) || d->preact)) return 1;
     if (!d->dact_in && d->act == 1 && d->preact) return 1;
     if (!d->dact_in && d->act == 0 && d->preact) return 1;
     if (!force && ((long)d->M * d->N < 512L * 512 || d->K < 512)) return 1;
@@ -1519,7 +1540,7 @@ extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale
   p.total_tiles = (int)total; p.nprob = 0; p.stagger = 0; p.debug_skip_stores = 0; p.debug_stamps = nullptr;
   const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
   hipStream_t s = (hipStream_t)stream;
-  const int epi = d->dact_in ? 3 : (d->act ? 2 : 0);
+  const int epi = g2_epi(d);                              // (x dact_in was accepted with act = 3 / 4 only: never 1)
   if (dyn) {                                              // device-side row counts (DYN kernels): whole tiles, no tail split
     p.m_dev = d->m_dev; p.k_dev = d->k_dev;
     p.colsum_part = (epi == 3) ? d->colsum_part : nullptr;
@@ -1527,6 +1548,7 @@ extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale
     dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
     if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
     else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
+    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
     return ivh_host::check_launch("gemm256_fp8 (device-side row count)") ? -1 : 0;
   }
@@ -1534,12 +1556,14 @@ extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale
     dim3 grid((unsigned)(p.total_tiles < cap ? p.total_tiles : cap), 1, 1), block(512);
     if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, true>), grid, block, 0, s, p);
     else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true, true>), grid, block, 0, s, p);
+    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true, true>), grid, block, 0, s, p);
     else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true, true>), grid, block, 0, s, p);
     return ivh_host::check_launch("gemm256_fp8 (tail split)") ? -1 : 0;
   }
   dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
   if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true>), grid, block, 0, s, p);
   else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true>), grid, block, 0, s, p);
+  else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true>), grid, block, 0, s, p);
   else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true>), grid, block, 0, s, p);
   return ivh_host::check_launch("gemm256_fp8") ? -1 : 0;
 }

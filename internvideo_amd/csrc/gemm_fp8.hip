@@ -134,8 +134,14 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(GemmF8Params p) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] += bv[r];
       }
+      float tg[4], td[4];                                // act = 4: gelu_tanh and its derivative from one exp (common.h)
+      if (p.act == 4 && (p.preact || !p.dact_in)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) gelu_tanh_pair(v[r], tg[r], td[r]);
+      }
       if (p.preact) {
-        if (p.act == 3) *reinterpret_cast<u32x2*>(p.preact + (long)m * p.ldp + n) = pack4(dgelu_erf(v[0]), dgelu_erf(v[1]), dgelu_erf(v[2]), dgelu_erf(v[3]));
+        if (p.act == 4) *reinterpret_cast<u32x2*>(p.preact + (long)m * p.ldp + n) = pack4(td[0], td[1], td[2], td[3]);
+        else if (p.act == 3) *reinterpret_cast<u32x2*>(p.preact + (long)m * p.ldp + n) = pack4(dgelu_erf(v[0]), dgelu_erf(v[1]), dgelu_erf(v[2]), dgelu_erf(v[3]));
         else *reinterpret_cast<u32x2*>(p.preact + (long)m * p.ldp + n) = pack4(v[0], v[1], v[2], v[3]);
       }
       if (p.dact_in) {
@@ -143,13 +149,16 @@ __global__ __launch_bounds__(256) void gemm_fp8_kernel(GemmF8Params p) {
         float u[4] = {__uint_as_float(uu[0] << 16), __uint_as_float(uu[0] & 0xffff0000u),
                       __uint_as_float(uu[1] << 16), __uint_as_float(uu[1] & 0xffff0000u)};
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] *= (p.act == 3) ? u[r] : ((p.act == 2) ? dgelu_tanh(u[r]) : dgelu_erf(u[r]));
+        for (int r = 0; r < 4; ++r) v[r] *= (p.act == 3 || p.act == 4) ? u[r] : ((p.act == 2) ? dgelu_tanh(u[r]) : dgelu_erf(u[r]));
       } else if (p.act == 1 || p.act == 3) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
       } else if (p.act == 2) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) v[r] = gelu_tanh(v[r]);
+      } else if (p.act == 4) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] = tg[r];
       }
       if (p.c_fp32) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(p.C) + (long)m * p.ldc + n) = f32x4{v[0], v[1], v[2], v[3]};
       else *reinterpret_cast<u32x2*>(reinterpret_cast<bf16_t*>(p.C) + (long)m * p.ldc + n) = pack4(v[0], v[1], v[2], v[3]);
@@ -465,8 +474,8 @@ static int gemm_fp8_impl(const ivh_gemm_desc* d, const float* scale_a, const flo
   IVH_REQUIRE(d->K % 16 == 0 && d->lda % 16 == 0 && d->ldb % 16 == 0, "gemm_fp8: K, lda, ldb must be multiples of 16 (bytes)");
   IVH_REQUIRE(d->N % 8 == 0 && d->ldc % 4 == 0, "gemm_fp8: N multiple of 8, ldc multiple of 4");
   IVH_REQUIRE(((uintptr_t)d->A % 16) == 0 && ((uintptr_t)d->B % 16) == 0 && ((uintptr_t)d->C % 16) == 0, "gemm_fp8: base pointers must be 16-byte aligned");
-  IVH_REQUIRE(d->act >= 0 && d->act <= 3 && (d->batch <= 1), "gemm_fp8: unsupported activation / batch");
-  IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in && d->act == 3),
+  IVH_REQUIRE(d->act >= 0 && d->act <= 4 && (d->batch <= 1), "gemm_fp8: unsupported activation / batch");
+  IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in && (d->act == 3 || d->act == 4)),
               "gemm_fp8: colsum_part is a by-product of the count-carrying (m_dev) x gelu' dgrad launch only");
   if (d->m_dev || d->k_dev) {                              // device-side row counts: the 256 x 256 kernel is the only one that stops at them
     IVH_REQUIRE(scale_a && scale_b, "gemm_fp8: null scale");

@@ -354,8 +354,10 @@ def _vgrad(p: torch.Tensor, g: torch.Tensor):
 
 def _act_d(act: str) -> str:
     """the derivative-exchanging flavour of an activation, when there is one: fc1's epilogue then stores gelu'(u) (a by-product of
-    its erf) instead of u, and fc2's dgrad epilogue is a plain multiply"""
-    return "gelu_erf_d" if act in ("gelu", "gelu_erf", "erf") else act
+    its erf, or of the tanh flavour's one exp) instead of u, and fc2's dgrad epilogue is a plain multiply"""
+    if act in ("gelu", "gelu_erf", "erf"):
+        return "gelu_erf_d"
+    return "gelu_tanh_d" if act in ("gelu_tanh", "tanh") else act
 
 
 def _mg(p: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -526,7 +528,7 @@ class MlpFn(torch.autograd.Function):
     def forward(ctx, x, w1, b1, w2, b2, act):
         x2 = x.reshape(-1, x.shape[-1])
         act = _act_d(act)
-        g, u = ops.gemm(x2, mat(w1), bias=vec(b1), act=act, want_preact=True)      # u = gelu'(pre-activation) for "gelu_erf_d"
+        g, u = ops.gemm(x2, mat(w1), bias=vec(b1), act=act, want_preact=True)      # u = gelu'(pre-activation) for "gelu_erf_d" / "gelu_tanh_d"
         y = ops.gemm(g, mat(w2), bias=vec(b2))
         ctx.save_for_backward(x2, u, g)
         ctx.p = (w1, b1, w2, b2)
@@ -608,7 +610,7 @@ DROPPATH_SKIP = __import__("os").environ.get("IVH_DROPPATH_SKIP", "1") != "0"
 
 def dp_skip_applies(meta, M: int, D: int, params) -> bool:
     """can this block stack run its DropPath branches on the kept samples only?  Needs the kernels that take device-side counts: the 256^2
-    bf16 GEMM (operands below 2 GiB, erf-GELU with the derivative exchanged) and the 32x32 attention kernels (head dim <= 128, 16-byte
+    bf16 GEMM (operands below 2 GiB, erf- or tanh-GELU with the derivative exchanged: every name _act_d maps) and the 32x32 attention kernels (head dim <= 128, 16-byte
     strides) -- otherwise the stack silently keeps the multiply-by-zero path (same results).
     meta["fp8"]: the quantisers and the 256^2 e4m3 GEMM take the counts too (ops.fp8_quantize / ops.gemm_fp8, m_dev / k_dev); their
     conditions are widths that are multiples of 16 and operands below 2 GiB (the bf16 outputs are the larger side of that bound; the e4m3
@@ -619,7 +621,7 @@ def dp_skip_applies(meta, M: int, D: int, params) -> bool:
     mode = meta.get("dp_skip", "auto")
     if not DROPPATH_SKIP or mode is False or mode is None:
         return False
-    if _act_d(meta["act"]) != "gelu_erf_d":
+    if _act_d(meta["act"]) not in ("gelu_erf_d", "gelu_tanh_d"):
         return False
     H, L = meta["H"], meta["L"]
     hd = D // H
@@ -1181,7 +1183,7 @@ def block_stack_infer(x0, block_params: Sequence, S: int, L: int, H: int, eps: f
         del att
         res2, n2, _ = ops.rmsnorm_add_fwd(res1, b1, vec(ls1) if ls1 is not None else None, None, L, vec(n2w), eps)
         del b1
-        g = lin(n2, fc1w, bias=vec(fc1b), act=act)
+        g = lin(n2, fc1w, bias=vec(fc1b), act=_act_d(act))   # (no gelu' copy is asked for: the exchanged flavours are the ones the 256^2 kernels carry)
         del n2
         branch = lin(g, fc2w, bias=vec(fc2b))
         del g

@@ -9,7 +9,8 @@ Differences from the reference that are visible to a caller:
   * the three `use_flash_attn / use_fused_rmsnorm / use_fused_mlp` flags are accepted and must be consistent
     (P:446-447) but do not select code paths: there is one (fused) path.  `fused_mlp_act` = "erf" (parity with the
     unfused Mlp / the CPU oracle, default) or "tanh" (what flash_attn's FusedMLP computes; use it for checkpoints
-    trained on the fused reference path, SURVEY.md 8(c));
+    trained on the fused reference path).  Both run on the same kernels -- the 256^2 GEMM epilogues with the
+    derivative exchanged, DropPath sample skipping, the e4m3 path -- and differ only in the activation's arithmetic;
   * `use_checkpoint` / `checkpoint_num` (P:294-296, 323-327) are honoured: the first `checkpoint_num` blocks keep only their outputs
     and are recomputed in backward, bit-identically (functional.BlockStackFn).  Off by default: 288 GB of HBM holds all block
     activations at the reference batch size, so the shipped recipes need no recomputation here;

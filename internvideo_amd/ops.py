@@ -31,7 +31,8 @@ def _pcall(name: str, work: float, unit: str, fname: str, *args, dyn=None) -> No
     e1.record()
     KERNEL_PROFILE.append((name, float(work), unit, e0, e1, dyn))
 # "gelu_erf_d": GELU(erf) whose `preact` output / `dact_in` input is gelu'(pre-activation) itself (include/internvideo_hip.h, act = 3)
-ACT = {None: 0, "none": 0, "gelu": 1, "gelu_erf": 1, "erf": 1, "gelu_tanh": 2, "tanh": 2, "gelu_erf_d": 3}
+# "gelu_tanh_d": the same exchange for GELU(tanh) (act = 4); "gelu_tanh" (act = 2) keeps the pre-activation copy and runs on the 128^2 kernels
+ACT = {None: 0, "none": 0, "gelu": 1, "gelu_erf": 1, "erf": 1, "gelu_tanh": 2, "tanh": 2, "gelu_erf_d": 3, "gelu_tanh_d": 4}
 
 
 def _chk(t: torch.Tensor, dtype, name: str, inner_contig: bool = True):
@@ -128,7 +129,7 @@ def gemm(a: torch.Tensor, b: torch.Tensor, *, a_kc: bool = True, b_kc: bool = Tr
         dyn = (k_dev, K)
     part = None
     if want_colsum:                         # bias gradient as a by-product of the 256^2 dgrad epilogue; -> (out, part | None)
-        if dact_in is not None and d.act == 3 and not batched and _L.load().ivh_gemm_select(C.byref(d)) == 2:
+        if dact_in is not None and d.act in (3, 4) and not batched and _L.load().ivh_gemm_select(C.byref(d)) == 2:
             part = torch.empty((2 * ((M + 255) // 256), N), dtype=F32, device=a.device)
             d.colsum_part = part.data_ptr()
         res = _gemm_launch(d, a_kc, b_kc, nb, M, N, K, out, pre, want_preact, dyn)

@@ -308,7 +308,7 @@ def _linear_autograd(ctx, dy):
 
 # ---- FusedMLP --------------------------------------------------------------------------------------------------------------------------
 def _mlp(x, w1, b1, w2, b2, act="gelu_erf"):
-    """-> (y, u, g): u = what fc2's dgrad epilogue multiplies by (gelu'(pre-activation) for the erf flavour, the pre-activation for tanh),
+    """-> (y, u, g): u = what fc2's dgrad epilogue multiplies by (gelu'(pre-activation), bf16, for the erf and the tanh flavour alike: act = 3 / 4),
     g = gelu(fc1(x)); both are saved for the backward"""
     from .functional import _act_d
     a = _act_d(act)
