@@ -26,6 +26,12 @@ int ivh_gemm256_debug_split(int on);           /* 0 = never split the tail round
 /* half-width tiles of the 256x256 kernel (ivh_gemm256_half_plan in internvideo_hip.h): 0 = off (A/B, tests), 1 = on, a workgroup's half tile
  * runs between its whole tiles (default), 2 = on, half tiles last */
 int ivh_gemm256_debug_half(int on);
+/* Host logic only (no device needed): the ten template arguments {a_kc, b_kc, epi, grouped, dbg, sched, fp8, split, half, dyn} of the
+ * gemm256_kernel instantiation the launchers would run for *d on `cap` workgroups (0 = the device's CUs, 256 without a device), chosen by the
+ * function the launchers themselves call.  mode 0 = the bf16 launch, 1 = the e4m3 launch as ivh_gemm_fp8 calls it under its default kernel
+ * choice (size test on for a count-free descriptor), n >= 2 = the grouped launch of d[0 .. n).  Returns 1, or 0 when the launcher would refuse
+ * the descriptor or hand it over to the 128x128 kernel (out10 is then not written). */
+int ivh_gemm256_debug_route(const ivh_gemm_desc* d, int mode, int cap, int* out10);
 int ivh_gemm256_debug_ablate(int mode);         /* K-loop ablation of the plain NT kernel: 0 off, 1 no MFMA, 2 no LDS-DMA, 3 no fragment reads (garbage results) */
 
 /* probes used by tests/test_hw_probe.py to pin the hardware semantics the kernels rely on */

@@ -145,6 +145,18 @@ int check_launch(const char* what);
 const unsigned* dropout_epoch();          // device pointer registered with ivh_set_dropout_epoch, or NULL
 }  // namespace ivh_host
 
+// ---- internals of the 256x256 GEMM (gemm256.hip) that gemm.hip / gemm_fp8.hip route through; not part of the C ABI headers --------
+#include "../../include/internvideo_hip.h"
+extern "C" {
+int ivh_gemm256_supported(const ivh_gemm_desc* d);                            // the epilogue / layout combinations the bf16 kernel is built for
+int ivh_gemm256_fits(const ivh_gemm_desc* d);                                 // every (batched) operand / output below 2 GiB - 16 MiB
+int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream);
+int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream);
+int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* stream);
+int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8);          // workspace with which the tail round is split along K (0 = no split)
+double ivh_gemm256_split_tail_frac(const ivh_gemm_desc* d, int fp8);          // K steps of the split tail round relative to a whole round
+}
+
 #define IVH_REQUIRE(cond, ...)            \
   do {                                    \
     if (!(cond)) {                        \

@@ -210,9 +210,6 @@ __global__ __launch_bounds__(256) void gemm_bf16_kernel(GemmParams p) {
 
 }  // namespace ivh
 
-extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream);   // gemm256.hip
-extern "C" int ivh_gemm256_supported(const ivh_gemm_desc* d);
-
 static int g_gemm_kernel_choice = 0;   // 0 = heuristic, 1 = 128^2 / 4-wave kernel, 2 = 256^2 / 8-wave ping-pong kernel
 extern "C" int ivh_set_gemm_kernel(int choice) {
   IVH_REQUIRE(choice >= 0 && choice <= 2, "set_gemm_kernel: choice must be 0 (auto), 1 (128^2) or 2 (256^2)");
@@ -236,13 +233,7 @@ static double gemm_time_model(int M, int N, int K, int batch, bool any_tr, bool 
   return rounds * per_round;
 }
 
-// which kernel ivh_gemm_bf16 would launch for this problem: 1 = 128^2, 2 = 256^2
-extern "C" int ivh_gemm256_fits(const ivh_gemm_desc* d);   // gemm256.hip
-
-extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8);      // gemm256.hip
-extern "C" double ivh_gemm256_split_tail_frac(const ivh_gemm_desc* d, int fp8);
-extern "C" double ivh_gemm256_half_rounds(const ivh_gemm_desc* d);                    // half-width tiles: launch length in rounds, or -1
-
+// which kernel ivh_gemm_bf16 would launch for this problem: 1 = 128^2, 2 = 256^2 (the ivh_gemm256_* queries: gemm256.hip, declared in common.h)
 static int gemm_select_impl(const ivh_gemm_desc* d, bool assume_ws) {
   if (!ivh_gemm256_supported(d)) return 1;
   if (d->m_dev || d->k_dev) return 2;                    // device-side row counts exist in the 256^2 kernel only
@@ -342,8 +333,6 @@ extern "C" int ivh_gemm_bf16(const ivh_gemm_desc* d, void* stream) {
   return ivh_host::check_launch("gemm_bf16");
 }
 
-
-extern "C" int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* stream);   // gemm256.hip
 
 extern "C" int ivh_gemm_grouped_bf16(const ivh_gemm_desc* d, int n, void* stream) {
   IVH_REQUIRE(d && n > 0, "gemm_grouped: empty problem list");

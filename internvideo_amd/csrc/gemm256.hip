@@ -28,7 +28,9 @@
 // Operand layouts as in gemm.hip: K-contiguous operands are staged [128 rows][64 k] with the 16-byte chunk XOR swizzle applied
 // on the DMA source address and on the ds_read_b128; rows-contiguous operands (dgrad B, wgrad A and B) are staged as they lie,
 // [64 k][128 rows], and transposed by ds_read_b64_tr_b16.
+#include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 #include "common.h"
 #include "../../include/internvideo_hip.h"
@@ -1162,12 +1164,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(Gemm256Params p) {
 
 }  // namespace ivh
 
-// Launcher used by ivh_gemm_bf16 (gemm.hip) when the 256^2 kernel is selected.  Arguments were validated there.
+
+// ---- host side: which gemm256_kernel runs for a descriptor, and its launch ------------------------------------------------------------
 // The kernel's EPI flavour for a descriptor.  act = 3 / 4 (erf / tanh GELU with the derivative exchanged) share the x dact_in epilogue;
 // forward launches with act = 4 run the tanh twin (EPI 4) of the GELU epilogue (EPI 2), in every launch mode EPI 2 is built for.
 static inline bool g2_act_d(int act) { return act == 3 || act == 4; }
 static inline int g2_epi(const ivh_gemm_desc* d) { return d->dact_in ? (g2_act_d(d->act) ? 3 : 1) : (d->act == 4 ? 4 : (d->act ? 2 : 0)); }
-static inline bool g2_gelu_epi(int epi) { return epi == 2 || epi == 4; }
 static int g_g2_stagger = -1, g_g2_skip_stores = 0;      // -1 = choose per launch
 static unsigned long long* g_g2_stamps = nullptr;
 static int g_g2_max_wg = 0;                               // measurement aid: cap the number of workgroups (0 = #CUs)
@@ -1185,7 +1187,6 @@ extern "C" int ivh_gemm256_debug_stamps(void* buf_128_u64) {
   return 0;
 }
 
-extern "C" int ivh_gemm256_supported(const ivh_gemm_desc* d);
 static int g2_n_cu() {
   static int n_cu = 0;
   if (n_cu == 0) {
@@ -1195,6 +1196,51 @@ static int g2_n_cu() {
     else n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
   }
   return n_cu;
+}
+static long g2_cap() { return g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu(); }   // workgroups of a persistent launch
+
+// Every gemm256_kernel instantiation that exists, once.  Taking the address instantiates the kernel; a launch mode, an epilogue or a layout
+// is "built" exactly when its row is here (g2_find), and a launch whose key has no row is an error (g2_launch), never another flavour.
+struct G2Key { int a_kc, b_kc, epi, grouped, dbg, sched, fp8, split, half, dyn; };       // = the template arguments, in their order
+typedef void (*G2Kernel)(ivh::Gemm256Params);
+struct G2Row { G2Key key; G2Kernel fn; };
+#define G2_K(a, b, epi, grp, dbg, sched, f8, split, half, dyn) \
+  {{a, b, epi, grp, dbg, sched, f8, split, half, dyn},         \
+   &ivh::gemm256_kernel<(a) != 0, (b) != 0, epi, (grp) != 0, dbg, sched, (f8) != 0, (split) != 0, (half) != 0, (dyn) != 0>}
+// the five bf16 flavours every launch mode is built for: plain NT / NN, fc1 forward GELU (erf 2, tanh 4), fc2 dgrad x gelu' (3); the four e4m3 ones
+#define G2_BF16(split, half, dyn)                                                                                                        \
+  G2_K(1, 1, 0, 0, 0, 0, 0, split, half, dyn), G2_K(1, 0, 0, 0, 0, 0, 0, split, half, dyn), G2_K(1, 1, 2, 0, 0, 0, 0, split, half, dyn), \
+      G2_K(1, 1, 4, 0, 0, 0, 0, split, half, dyn), G2_K(1, 0, 3, 0, 0, 0, 0, split, half, dyn)
+#define G2_E4M3(split, dyn) \
+  G2_K(1, 1, 0, 0, 0, 0, 1, split, 0, dyn), G2_K(1, 1, 2, 0, 0, 0, 1, split, 0, dyn), G2_K(1, 1, 4, 0, 0, 0, 1, split, 0, dyn), G2_K(1, 1, 3, 0, 0, 0, 1, split, 0, dyn)
+static const G2Row g2_table[] = {
+    G2_BF16(0, 0, 0), G2_BF16(1, 0, 0), G2_BF16(0, 1, 0), G2_BF16(0, 0, 1), G2_BF16(1, 0, 1),      // whole tiles, SPLIT, HALF, DYN, DYN + SPLIT
+    G2_K(0, 1, 0, 0, 0, 0, 0, 0, 0, 0), G2_K(0, 0, 0, 0, 0, 0, 0, 0, 0, 0), G2_K(1, 0, 1, 0, 0, 0, 0, 0, 0, 0),   // whole tiles only: TN, TT, dgrad with erf recomputed
+    G2_K(0, 0, 0, 0, 0, 0, 0, 0, 0, 1),                                                            // k_dev: the weight-gradient layout
+    // measurement variants of the plain NT kernel: K-loop ablations DBG 1-6 (ivh_gemm256_debug_ablate), rolling K loop (ivh_gemm256_debug_sched)
+    G2_K(1, 1, 0, 0, 1, 0, 0, 0, 0, 0), G2_K(1, 1, 0, 0, 2, 0, 0, 0, 0, 0), G2_K(1, 1, 0, 0, 3, 0, 0, 0, 0, 0), G2_K(1, 1, 0, 0, 4, 0, 0, 0, 0, 0),
+    G2_K(1, 1, 0, 0, 5, 0, 0, 0, 0, 0), G2_K(1, 1, 0, 0, 6, 0, 0, 0, 0, 0), G2_K(1, 1, 0, 0, 0, 1, 0, 0, 0, 0),
+    G2_E4M3(0, 0), G2_E4M3(1, 0), G2_E4M3(0, 1),                                                   // e4m3: whole tiles, SPLIT, DYN
+    G2_K(0, 0, 0, 1, 0, 0, 0, 0, 0, 0), G2_K(0, 0, 0, 1, 0, 0, 0, 0, 0, 1),                        // grouped weight gradients; with per-problem K (DYN)
+};
+#undef G2_E4M3
+#undef G2_BF16
+#undef G2_K
+static G2Kernel g2_find(const G2Key& k) {
+  for (const G2Row& r : g2_table)
+    if (memcmp(&r.key, &k, sizeof(G2Key)) == 0) return r.fn;
+  return nullptr;
+}
+// the key of `d` in launch mode (split, half, dyn), measurement variants off
+static G2Key g2_key(const ivh_gemm_desc* d, int fp8, int split, int half, int dyn) {
+  return G2Key{d->a_kc != 0, d->b_kc != 0, g2_epi(d), 0, 0, 0, fp8 != 0, split, half, dyn};
+}
+static int g2_launch(const G2Key& k, long grid, hipStream_t s, const ivh::Gemm256Params& p, const char* what) {
+  const G2Kernel fn = g2_find(k);
+  IVH_REQUIRE(fn, "%s: gemm256_kernel<%d, %d, %d, %d, %d, %d, %d, %d, %d, %d> is not built", what, k.a_kc, k.b_kc, k.epi, k.grouped, k.dbg, k.sched,
+              k.fp8, k.split, k.half, k.dyn);
+  hipLaunchKernelGGL(fn, dim3((unsigned)grid, 1, 1), dim3(512), 0, s, p);
+  return ivh_host::check_launch(what);
 }
 
 // Tail split along K.  A persistent launch runs ceil(tiles / grid) rounds and the last one is as long as the others however few
@@ -1219,13 +1265,20 @@ static int g2_split_plan(long total, long cap, int nk, int* main_tiles, int* S, 
   *main_tiles = (int)(R * cap); *S = (int)s; *nk2s = per; *tail_tiles = (int)rem;
   return 1;
 }
+struct G2Split { int main_tiles, S, per, tail; };
+// the host-side plan for the tiles of *d (batch 1) on `cap` workgroups.  `fp8`: e4m3 operands (a K step is 128 values).
+static int g2_split_plan_desc(const ivh_gemm_desc* d, int fp8, long cap, G2Split* sp) {
+  const long total = (long)((d->M + ivh::G2_BM - 1) / ivh::G2_BM) * ((d->N + ivh::G2_BN - 1) / ivh::G2_BN);
+  const int bke = fp8 ? 128 : 64;
+  return g2_split_plan(total, cap, (d->K + bke - 1) / bke, &sp->main_tiles, &sp->S, &sp->per, &sp->tail);
+}
 
 static int g_g2_split = [] { const char* e = getenv("IVH_NO_SPLIT"); return (e && e[0] == '1') ? 0 : 1; }();   // 0 = never split (A/B, tests; env IVH_NO_SPLIT=1)
 extern "C" int ivh_gemm256_debug_split(int on) { g_g2_split = on ? 1 : 0; return 0; }
 
-// bytes of workspace (d->split_ws) with which ivh_gemm256_launch / ivh_gemm256_fp8_launch would split the tail of this problem along K;
-// 0 = no split (not built for this flavour, nothing to gain, or switched off).  `fp8`: e4m3 operands (a K step is 128 values).
-extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8) {
+// bytes of workspace (d->split_ws) with which a launch of *d on `cap` workgroups would split the tail along K, and the host-side plan (`sp`,
+// untouched when the plan is made on the device); 0 = no split (not built for this flavour, nothing to gain, or switched off).
+static int64_t g2_split_need(const ivh_gemm_desc* d, int fp8, long cap, G2Split* sp) {
   if (!g_g2_split || !d || !d->a_kc || d->batch > 1 || d->c_fp32 || g_g2_dbg || g_g2_sched || g_g2_stamps || g_g2_stagger > 0) return 0;
   if (d->k_dev) return 0;
   if (d->m_dev) {
@@ -1233,51 +1286,24 @@ extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8) {
     // sized for the largest plan a launch on `cap` workgroups can make (one 256 KiB slab per workgroup).  Long K only: a slice needs
     // nk - 2 * per >= 40 with per >= 2 loop trips.
     if (fp8) return 0;
-    const int epi_d = g2_epi(d);
-    if (epi_d == 1 || (g2_gelu_epi(epi_d) && !d->b_kc) || (epi_d == 3 && d->b_kc)) return 0;
+    if (!g2_find(g2_key(d, 0, 1, 0, 1))) return 0;
     if ((d->K + 63) / 64 < 44) return 0;
-    const long capd = g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu();
-    return 4096 + (int64_t)capd * 262144;
+    return 4096 + (int64_t)cap * 262144;
   }
-  if (fp8 && !d->b_kc) return 0;
-  const int epi = g2_epi(d);
-  if (epi == 1 || (g2_gelu_epi(epi) && !d->b_kc) || (epi == 3 && (fp8 ? false : d->b_kc))) return 0;
-  const long total = (long)((d->M + ivh::G2_BM - 1) / ivh::G2_BM) * ((d->N + ivh::G2_BN - 1) / ivh::G2_BN);
-  const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu();
-  const int bke = fp8 ? 128 : 64;
-  int mt, S, per, tail;
-  if (!g2_split_plan(total, cap, (d->K + bke - 1) / bke, &mt, &S, &per, &tail)) return 0;
-  return 4096 + (int64_t)tail * S * 262144;
+  if (!g2_find(g2_key(d, fp8, 1, 0, 0))) return 0;
+  if (!g2_split_plan_desc(d, fp8, cap, sp)) return 0;
+  return 4096 + (int64_t)sp->tail * sp->S * 262144;
+}
+extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8) {
+  G2Split sp;
+  return g2_split_need(d, fp8, g2_cap(), &sp);
 }
 
 // K steps of the split tail round relative to a whole round (1.0 = no split): the launch-time model of gemm.hip
 extern "C" double ivh_gemm256_split_tail_frac(const ivh_gemm_desc* d, int fp8) {
-  if (ivh_gemm256_split_ws_bytes(d, fp8) <= 0) return 1.0;
-  const long total = (long)((d->M + ivh::G2_BM - 1) / ivh::G2_BM) * ((d->N + ivh::G2_BN - 1) / ivh::G2_BN);
-  const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu();
-  const int bke = fp8 ? 128 : 64;
-  const int nk = (d->K + bke - 1) / bke;
-  int mt, S, per, tail;
-  if (!g2_split_plan(total, cap, nk, &mt, &S, &per, &tail)) return 1.0;
-  return (double)(2 * per) / (double)nk;
-}
-
-// fills the split fields of p (total_tiles becomes the number of linear ids) and clears the counters; returns 1 if the launch is a SPLIT one
-static int g2_apply_split(const ivh_gemm_desc* d, int fp8, ivh::Gemm256Params& p, long cap, hipStream_t s) {
-  p.split_main = p.total_tiles; p.split_s = 0; p.split_nk2 = 0; p.split_ws = nullptr; p.split_cnt = nullptr; p.split_ws_bytes = 0;
-  if (!d->split_ws) return 0;
-  const int64_t need = ivh_gemm256_split_ws_bytes(d, fp8);
-  if (need <= 0 || d->split_ws_bytes < need || ((uintptr_t)d->split_ws % 16) != 0) return 0;
-  const int bke = fp8 ? 128 : 64;
-  int mt, S, per, tail;
-  if (!g2_split_plan(p.total_tiles, cap, (d->K + bke - 1) / bke, &mt, &S, &per, &tail)) return 0;
-  if (hipMemsetAsync(d->split_ws, 0, 4096, s) != hipSuccess) return 0;
-  p.split_main = mt; p.split_s = S; p.split_nk2 = per;
-  p.split_cnt = reinterpret_cast<unsigned*>(d->split_ws);
-  p.split_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->split_ws) + 4096);
-  p.split_ws_bytes = (long)tail * S * 262144;
-  p.total_tiles = mt + tail * S;
-  return 1;
+  G2Split sp;
+  if (ivh_gemm256_split_ws_bytes(d, fp8) <= 0 || !g2_split_plan_desc(d, fp8, g2_cap(), &sp)) return 1.0;
+  return (double)(2 * sp.per) / (double)((d->K + (fp8 ? 128 : 64) - 1) / (fp8 ? 128 : 64));
 }
 
 // Half-width tiles (gemm256_kernel, HALF).  Static round-robin cost of a launch in whole-tile units: `nfull` ids of cost 1 followed by
@@ -1323,22 +1349,20 @@ static int g_g2_half = [] { const char* e = getenv("IVH_NO_HALF"); return (e && 
 extern "C" int ivh_gemm256_debug_half(int mode) { g_g2_half = (mode >= 0 && mode <= 3) ? mode : 1; return 0; }   // 3 = interleaved by XCD block (A/B)
 static int g2_half_flavour(const ivh_gemm_desc* d) {     // the epilogue / layout combinations the HALF kernels are instantiated for
   if (!g_g2_half || !d->a_kc || d->c_fp32 || d->batch > 1 || d->m_dev || d->k_dev) return 0;
-  const int epi = g2_epi(d);
-  return epi == 0 || (g2_gelu_epi(epi) && d->b_kc) || (epi == 3 && !d->b_kc);
+  return g2_find(g2_key(d, 0, 0, 1, 0)) != nullptr;
 }
 // host-side view of the plan ivh_gemm256_launch would use for `d` on `cap` workgroups (0 = the device's CUs):
 // out = {tiles_nf, half_begin, half_split, total_ids}; returns 1 when half-width tiles are used, else 0.
 extern "C" int ivh_gemm256_half_plan(const ivh_gemm_desc* d, int cap, int* out4) {
   if (!d || !out4 || !g2_half_flavour(d) || !ivh_gemm256_supported(d)) return 0;
-  const long c = cap > 0 ? cap : (g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu());
-  return g2_half_plan(d->M, d->N, c, out4, out4 + 1, out4 + 2, out4 + 3);
+  return g2_half_plan(d->M, d->N, cap > 0 ? cap : g2_cap(), out4, out4 + 1, out4 + 2, out4 + 3);
 }
 
 // modelled length of the launch in whole-tile rounds when half-width tiles apply, else -1 (the launch-time model of gemm.hip)
 extern "C" double ivh_gemm256_half_rounds(const ivh_gemm_desc* d) {
   int o[4];
   if (!ivh_gemm256_half_plan(d, 0, o)) return -1.0;
-  return g2_rr_cost(o[1], (long)o[3] - o[1], g_g2_max_wg > 0 ? g_g2_max_wg : g2_n_cu());
+  return g2_rr_cost(o[1], (long)o[3] - o[1], g2_cap());
 }
 
 // The combinations the 256x256 kernel is built for (everything else runs on the 128x128 kernel of gemm.hip).
@@ -1351,228 +1375,148 @@ extern "C" int ivh_gemm256_supported(const ivh_gemm_desc* d) {
 }
 
 // The 256^2 kernel addresses every operand through one buffer descriptor with 32-bit byte offsets: each (batched) operand / output
-// extent must stay below 2 GiB - 16 MiB.  ivh_gemm_bf16 splits larger problems along M (K-contiguous A) or falls back to the 128^2
-// kernel, which uses 64-bit pointers.
-extern "C" int ivh_gemm256_fits(const ivh_gemm_desc* d) {
+// extent must stay below 2 GiB - 16 MiB, each leading dimension below 2^31.  The extents of *d in bytes (0 for an absent preact / dact_in /
+// bias) with `es` bytes per operand element (2: bf16, 1: e4m3), and whether they fit.
+struct G2Extents { long a, b, c, p, d, bias; bool operands_fit, outputs_fit, ld_fit; };
+static G2Extents g2_extents(const ivh_gemm_desc* d, int es) {
   const long lim = (1L << 31) - (1L << 24);
-  const int nb = d->batch > 0 ? d->batch : 1;
+  const long nb1 = (d->batch > 0 ? d->batch : 1) - 1;
   const long a_elems = d->a_kc ? ((long)d->M - 1) * d->lda + d->K : ((long)d->K - 1) * d->lda + d->M;
   const long b_elems = d->b_kc ? ((long)d->N - 1) * d->ldb + d->K : ((long)d->K - 1) * d->ldb + d->N;
-  if (((long)(nb - 1) * d->strideA + a_elems) * 2 >= lim || ((long)(nb - 1) * d->strideB + b_elems) * 2 >= lim) return 0;
-  if (((long)(nb - 1) * d->strideC + ((long)d->M - 1) * d->ldc + d->N) * (d->c_fp32 ? 4 : 2) >= lim) return 0;
-  if (d->preact && ((long)(nb - 1) * d->stride_preact + ((long)d->M - 1) * d->ldp + d->N) * 2 >= lim) return 0;
-  if (d->dact_in && ((long)(nb - 1) * d->stride_dact + ((long)d->M - 1) * d->ldd + d->N) * 2 >= lim) return 0;
-  return 1;
+  G2Extents e;
+  e.a = (nb1 * d->strideA + a_elems) * es; e.b = (nb1 * d->strideB + b_elems) * es;
+  e.c = (nb1 * d->strideC + ((long)d->M - 1) * d->ldc + d->N) * (d->c_fp32 ? 4 : 2);
+  e.p = d->preact ? (nb1 * d->stride_preact + ((long)d->M - 1) * d->ldp + d->N) * 2 : 0;
+  e.d = d->dact_in ? (nb1 * d->stride_dact + ((long)d->M - 1) * d->ldd + d->N) * 2 : 0;
+  e.bias = d->bias ? (nb1 * d->stride_bias + d->N) * 4 : 0;
+  e.operands_fit = e.a < lim && e.b < lim;
+  e.outputs_fit = e.c < lim && e.p < lim && e.d < lim;
+  e.ld_fit = d->lda < (1L << 31) && d->ldb < (1L << 31) && d->ldc < (1L << 31) && d->ldp < (1L << 31) && d->ldd < (1L << 31);
+  return e;
+}
+// ivh_gemm_bf16 splits larger problems along M (K-contiguous A) or falls back to the 128^2 kernel, which uses 64-bit pointers.
+extern "C" int ivh_gemm256_fits(const ivh_gemm_desc* d) {
+  const G2Extents e = g2_extents(d, 2);
+  return e.operands_fit && e.outputs_fit;
 }
 
-extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) {
-  using namespace ivh;
-  IVH_REQUIRE(ivh_gemm256_supported(d), "gemm256: unsupported epilogue / layout combination");
-  const long a_elems = d->a_kc ? ((long)d->M - 1) * d->lda + d->K : ((long)d->K - 1) * d->lda + d->M;
-  const long b_elems = d->b_kc ? ((long)d->N - 1) * d->ldb + d->K : ((long)d->K - 1) * d->ldb + d->N;
-  const int nb = d->batch > 0 ? d->batch : 1;
-  const long a_bytes = ((long)(nb - 1) * d->strideA + a_elems) * 2, b_bytes = ((long)(nb - 1) * d->strideB + b_elems) * 2;
-  IVH_REQUIRE(a_bytes < (1L << 31) - (1L << 24) && b_bytes < (1L << 31) - (1L << 24), "gemm256: (batched) operand larger than 2 GiB");
-  IVH_REQUIRE(d->strideA >= 0 && d->strideB >= 0, "gemm256: negative batch stride");
-  Gemm256Params p;
-  IVH_REQUIRE(d->lda < (1L << 31) && d->ldb < (1L << 31) && d->ldc < (1L << 31) && d->ldp < (1L << 31) && d->ldd < (1L << 31),
-              "gemm256: leading dimension does not fit 31 bits");
+// One set-up of a value-initialised Gemm256Params from a descriptor and its extents: every linear id a whole tile (the split / half-width
+// "off" state is set here and nowhere else; g2_route overwrites it with a plan).  The e4m3 scales are the caller's.
+static void g2_fill(ivh::Gemm256Params& p, const ivh_gemm_desc* d, const G2Extents& e, int fp8) {
   p.A = d->A; p.B = d->B; p.lda = (int)d->lda; p.ldb = (int)d->ldb; p.M = d->M; p.N = d->N; p.K = d->K;
   p.C = d->C; p.ldc = (int)d->ldc; p.c_fp32 = d->c_fp32; p.bias = d->bias; p.act = d->act;
   p.preact = d->preact; p.ldp = (int)d->ldp; p.dact_in = d->dact_in; p.ldd = (int)d->ldd;
-  p.alpha = d->alpha; p.tiles_m = (d->M + G2_BM - 1) / G2_BM; p.tiles_n = (d->N + G2_BN - 1) / G2_BN;
+  p.alpha = d->alpha; p.tiles_m = (d->M + ivh::G2_BM - 1) / ivh::G2_BM; p.tiles_n = (d->N + ivh::G2_BN - 1) / ivh::G2_BN;
   p.strideA = d->strideA; p.strideB = d->strideB; p.strideC = d->strideC; p.stride_bias = d->stride_bias;
   p.stride_preact = d->stride_preact; p.stride_dact = d->stride_dact;
-  p.batch = nb; p.a_bytes = a_bytes; p.b_bytes = b_bytes;
-  p.colsum_part = (d->dact_in && g2_act_d(d->act) && nb == 1) ? d->colsum_part : nullptr;
-  const long lim = (1L << 31) - (1L << 24);
-  p.c_bytes = ((long)(nb - 1) * d->strideC + ((long)d->M - 1) * d->ldc + d->N) * (d->c_fp32 ? 4 : 2);
-  p.p_bytes = d->preact ? ((long)(nb - 1) * d->stride_preact + ((long)d->M - 1) * d->ldp + d->N) * 2 : 0;
-  p.d_bytes = d->dact_in ? ((long)(nb - 1) * d->stride_dact + ((long)d->M - 1) * d->ldd + d->N) * 2 : 0;
-  p.bias_bytes = d->bias ? ((long)(nb - 1) * d->stride_bias + d->N) * 4 : 0;
-  IVH_REQUIRE(p.c_bytes < lim && p.p_bytes < lim && p.d_bytes < lim, "gemm256: (batched) output larger than 2 GiB");
-  IVH_REQUIRE(d->strideC >= 0 && d->stride_preact >= 0 && d->stride_dact >= 0 && d->stride_bias >= 0, "gemm256: negative batch stride");
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) n_cu = 256;
-    else n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const long total = (long)p.tiles_m * p.tiles_n * p.batch;
-  p.total_tiles = (int)total; p.nprob = 0;
-  p.stagger = g_g2_stagger > 0 ? g_g2_stagger : 0;       // measured: the skew never pays once the epilogue stores are row-major
-  p.debug_skip_stores = g_g2_skip_stores;
-  p.debug_stamps = g_g2_stamps;
-  { const char* e = g_g2_stamps ? getenv("IVH_G2_STAMP_WG") : nullptr; p.debug_stamp_wg = e ? atoi(e) : 0; }
-  const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
-  hipStream_t s = (hipStream_t)stream;
-  const int epi = g2_epi(d);
+  p.batch = d->batch > 0 ? d->batch : 1;
+  p.a_bytes = e.a; p.b_bytes = e.b; p.c_bytes = e.c; p.p_bytes = e.p; p.d_bytes = e.d; p.bias_bytes = e.bias;
+  p.colsum_part = (g2_epi(d) == 3 && p.batch == 1) ? d->colsum_part : nullptr;
   p.m_dev = d->m_dev; p.k_dev = d->k_dev;
-  if (d->m_dev || d->k_dev) {                             // device-side row counts (DYN kernels): no tail split, no half-width tiles
-    IVH_REQUIRE(nb == 1 && !g_g2_dbg && !g_g2_sched, "gemm256: device-side row counts (m_dev / k_dev) are built for single, unbatched problems");
-    IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm256: m_dev and k_dev are mutually exclusive");
-    IVH_REQUIRE(!d->m_dev || d->a_kc, "gemm256: m_dev counts the rows of a K-contiguous A (forward / dgrad launches)");
-    IVH_REQUIRE(!d->k_dev || (!d->a_kc && !d->b_kc && epi == 0), "gemm256: k_dev counts the rows of rows-contiguous operands (weight gradients, plain epilogue)");
-    IVH_REQUIRE(epi != 1, "gemm256: m_dev with the erf-recomputing dgrad epilogue (act = 1) is not built; use act = 3 / 4");
-    p.half_begin = p.total_tiles; p.half_split = 0; p.tiles_nf = p.tiles_n; p.half_interleave = 0;
-    p.split_main = p.total_tiles; p.split_s = 0; p.split_nk2 = 0; p.split_ws = nullptr; p.split_cnt = nullptr; p.split_ws_bytes = 0;
-    dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
-    if (d->m_dev && d->split_ws && total >= cap) {        // tail split planned on the device (long K, workspace for the largest plan supplied)
-      const int64_t need = ivh_gemm256_split_ws_bytes(d, 0);
-      if (need > 0 && d->split_ws_bytes >= need && ((uintptr_t)d->split_ws % 16) == 0 && hipMemsetAsync(d->split_ws, 0, 4096, s) == hipSuccess) {
-        p.split_cnt = reinterpret_cast<unsigned*>(d->split_ws);
-        p.split_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->split_ws) + 4096);
-        p.split_ws_bytes = (long)cap * 262144;
-        if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
-        else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
-        else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
-        else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
-        else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, true, false, true>), grid, block, 0, s, p);
-        return ivh_host::check_launch("gemm256_bf16 (device-side row count, tail split)");
-      }
-    }
-    if (d->k_dev) hipLaunchKernelGGL((gemm256_kernel<false, false, 0, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, false, false, true>), grid, block, 0, s, p);
-    return ivh_host::check_launch("gemm256_bf16 (device-side row count)");
-  }
-  if (g2_apply_split(d, 0, p, cap, s)) {                  // tail tiles cut into K slices (SPLIT kernels)
-    dim3 grid((unsigned)(p.total_tiles < cap ? p.total_tiles : cap), 1, 1), block(512);
-    if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, true>), grid, block, 0, s, p);
-    else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, true>), grid, block, 0, s, p);
-    else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, true>), grid, block, 0, s, p);
-    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, true>), grid, block, 0, s, p);
-    return ivh_host::check_launch("gemm256_bf16 (tail split)");
-  }
+  p.total_tiles = p.tiles_m * p.tiles_n * p.batch; p.nprob = 0;
+  p.split_main = p.total_tiles; p.split_s = 0; p.split_nk2 = 0; p.split_ws = nullptr; p.split_cnt = nullptr; p.split_ws_bytes = 0;
   p.half_begin = p.total_tiles; p.half_split = 0; p.tiles_nf = p.tiles_n; p.half_interleave = 0;
-  if (g2_half_flavour(d) && !g_g2_dbg && !g_g2_sched && g_g2_stagger <= 0) {
-    int tnf, hb, hs, ids;
-    if (g2_half_plan(d->M, d->N, cap, &tnf, &hb, &hs, &ids)) {                      // half-width tiles (HALF kernels)
-      p.tiles_nf = tnf; p.half_begin = hb; p.half_split = hs; p.total_tiles = ids; p.half_interleave = g_g2_half == 1 ? 1 : (g_g2_half == 3 ? 2 : 0);
-      dim3 grid((unsigned)(ids < cap ? ids : cap), 1, 1), block(512);
-      if (epi == 0 && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, false, false, true>), grid, block, 0, s, p);
-      else if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, false, 0, false, 0, 0, false, false, true>), grid, block, 0, s, p);
-      else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, false, false, true>), grid, block, 0, s, p);
-      else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, false, false, true>), grid, block, 0, s, p);
-      else hipLaunchKernelGGL((gemm256_kernel<true, false, 3, false, 0, 0, false, false, true>), grid, block, 0, s, p);
-      return ivh_host::check_launch("gemm256_bf16 (half-width tiles)");
-    }
+  if (!fp8) {                                            // the measurement aids act on the bf16 launches
+    p.stagger = g_g2_stagger > 0 ? g_g2_stagger : 0;     // measured: the skew never pays once the epilogue stores are row-major
+    p.debug_skip_stores = g_g2_skip_stores;
+    p.debug_stamps = g_g2_stamps;
+    { const char* w = g_g2_stamps ? getenv("IVH_G2_STAMP_WG") : nullptr; p.debug_stamp_wg = w ? atoi(w) : 0; }
   }
-  dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
-  if (epi == 0) {
-    if (d->a_kc && d->b_kc && g_g2_dbg == 1) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 1>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_dbg == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 2>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_dbg == 3) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 3>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_dbg == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 4>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_dbg == 5) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 5>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_dbg == 6) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 6>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc && g_g2_sched == 1) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 1>), grid, block, 0, s, p);
-    else if (d->a_kc && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, true, 0>), grid, block, 0, s, p);
-    else if (d->a_kc && !d->b_kc) hipLaunchKernelGGL((gemm256_kernel<true, false, 0>), grid, block, 0, s, p);
-    else if (!d->a_kc && d->b_kc) hipLaunchKernelGGL((gemm256_kernel<false, true, 0>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<false, false, 0>), grid, block, 0, s, p);
-  } else if (epi == 2) {
-    hipLaunchKernelGGL((gemm256_kernel<true, true, 2>), grid, block, 0, s, p);
-  } else if (epi == 4) {
-    hipLaunchKernelGGL((gemm256_kernel<true, true, 4>), grid, block, 0, s, p);
-  } else if (epi == 3) {
-    hipLaunchKernelGGL((gemm256_kernel<true, false, 3>), grid, block, 0, s, p);
-  } else {
-    hipLaunchKernelGGL((gemm256_kernel<true, false, 1>), grid, block, 0, s, p);
-  }
-  return ivh_host::check_launch("gemm256_bf16");
 }
 
-
+// The routing decision of ivh_gemm256_launch (fp8 = 0) and ivh_gemm256_fp8_launch (fp8 = 1, `force` as there) on `cap` workgroups: the key of
+// the kernel and its parameters, in the order of precedence DYN (with the device-planned split when a workspace is supplied and total >= cap),
+// host tail split, half-width tiles, plain.  `split_ok` = 0: as if no workspace had been supplied.  Returns 0, 1 when the problem is not for this
+// kernel (e4m3 only), < 0 with the error set when the launch is refused.
 // e4m3 operands (ivh_gemm_fp8, gemm_fp8.hip): bf16 output, K-contiguous operands, plain / GELU(+gelu') / x gelu' epilogues, problems
 // large enough for 256 x 256 tiles (`force`: any size -- the size test is a speed heuristic, the K loop runs any K >= 1, ghost K steps
 // multiply zeros).  Returns 1 when the problem is not for this kernel (the caller uses the 128^2 e4m3 kernel).
 // A descriptor that carries a device-side row count (m_dev / k_dev) runs here or nowhere: the 128^2 kernel would walk the stale rows behind
 // the count, so whatever this kernel is not built for is an error (< 0) for such a descriptor, never a 1.
-extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream) {
-  using namespace ivh;
+static int g2_route(const ivh_gemm_desc* d, int fp8, int force, long cap, int split_ok, ivh::Gemm256Params& p, G2Key* key) {
   const bool dyn = d->m_dev || d->k_dev;
-  if (dyn) {
-    IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm_fp8: m_dev and k_dev are mutually exclusive");
-    IVH_REQUIRE(d->a_kc && d->b_kc && !d->c_fp32 && d->batch <= 1 && d->act != 2,
-                "gemm_fp8: device-side row counts need the 256x256 e4m3 kernel: K-contiguous operands, bf16 output, batch 1, plain, erf-GELU or derivative-exchanging (act = 3 / 4) epilogue");
-    IVH_REQUIRE(!(d->dact_in && (!g2_act_d(d->act) || d->preact)) && !(!d->dact_in && !g2_act_d(d->act) && d->preact),
-                "gemm_fp8: device-side row counts: a pre-activation copy exists with act = 3 / 4 (GELU + gelu' copy) only, x gelu' with act = 3 / 4 only");
-    IVH_REQUIRE(!d->k_dev || (!d->dact_in && d->act == 0 && !d->bias && !d->preact), "gemm_fp8: k_dev counts the token rows of a weight gradient (plain epilogue, no bias)");
-    IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in), "gemm_fp8: colsum_part is a by-product of the m_dev x gelu' dgrad launch");
+  const G2Extents e = g2_extents(d, fp8 ? 1 : 2);
+  if (!fp8) {
+    IVH_REQUIRE(ivh_gemm256_supported(d), "gemm256: unsupported epilogue / layout combination");
+    IVH_REQUIRE(e.operands_fit, "gemm256: (batched) operand larger than 2 GiB");
+    IVH_REQUIRE(d->strideA >= 0 && d->strideB >= 0, "gemm256: negative batch stride");
+    IVH_REQUIRE(e.ld_fit, "gemm256: leading dimension does not fit 31 bits");
+    IVH_REQUIRE(e.outputs_fit, "gemm256: (batched) output larger than 2 GiB");
+    IVH_REQUIRE(d->strideC >= 0 && d->stride_preact >= 0 && d->stride_dact >= 0 && d->stride_bias >= 0, "gemm256: negative batch stride");
   } else {
-    if (!d->a_kc || !d->b_kc || d->c_fp32 || d->batch > 1 || d->colsum_part || d->act == 2) return 1;
-    if (d->dact_in && (!g2_act_d(d->act) || d->preact)) return 1;
-    if (!d->dact_in && d->act == 1 && d->preact) return 1;
-    if (!d->dact_in && d->act == 0 && d->preact) return 1;
-    if (!force && ((long)d->M * d->N < 512L * 512 || d->K < 512)) return 1;
+    if (dyn) {
+      IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm_fp8: m_dev and k_dev are mutually exclusive");
+      IVH_REQUIRE(d->a_kc && d->b_kc && !d->c_fp32 && d->batch <= 1 && d->act != 2,
+                  "gemm_fp8: device-side row counts need the 256x256 e4m3 kernel: K-contiguous operands, bf16 output, batch 1, plain, erf-GELU or derivative-exchanging (act = 3 / 4) epilogue");
+      IVH_REQUIRE(!(d->dact_in && (!g2_act_d(d->act) || d->preact)) && !(!d->dact_in && !g2_act_d(d->act) && d->preact),
+                  "gemm_fp8: device-side row counts: a pre-activation copy exists with act = 3 / 4 (GELU + gelu' copy) only, x gelu' with act = 3 / 4 only");
+      IVH_REQUIRE(!d->k_dev || (!d->dact_in && d->act == 0 && !d->bias && !d->preact), "gemm_fp8: k_dev counts the token rows of a weight gradient (plain epilogue, no bias)");
+      IVH_REQUIRE(!d->colsum_part || (d->m_dev && d->dact_in), "gemm_fp8: colsum_part is a by-product of the m_dev x gelu' dgrad launch");
+    } else {
+      if (!d->a_kc || !d->b_kc || d->c_fp32 || d->batch > 1 || d->colsum_part || d->act == 2) return 1;
+      if (d->dact_in && (!g2_act_d(d->act) || d->preact)) return 1;
+      if (!d->dact_in && d->act == 1 && d->preact) return 1;
+      if (!d->dact_in && d->act == 0 && d->preact) return 1;
+      if (!force && ((long)d->M * d->N < 512L * 512 || d->K < 512)) return 1;
+    }
+    const bool fits = e.operands_fit && e.outputs_fit && e.ld_fit;
+    if (dyn) IVH_REQUIRE(fits, "gemm_fp8: device-side row counts: every operand / output must stay below 2 GiB (32-bit descriptor offsets)");
+    if (!fits) return 1;
   }
-  const long lim = (1L << 31) - (1L << 24);
-  const long a_bytes = ((long)d->M - 1) * d->lda + d->K, b_bytes = ((long)d->N - 1) * d->ldb + d->K;
-  Gemm256Params p{};
-  p.c_bytes = (((long)d->M - 1) * d->ldc + d->N) * 2;
-  p.p_bytes = d->preact ? (((long)d->M - 1) * d->ldp + d->N) * 2 : 0;
-  p.d_bytes = d->dact_in ? (((long)d->M - 1) * d->ldd + d->N) * 2 : 0;
-  const bool fits = a_bytes < lim && b_bytes < lim && p.c_bytes < lim && p.p_bytes < lim && p.d_bytes < lim &&
-                    d->lda < (1L << 31) && d->ldb < (1L << 31) && d->ldc < (1L << 31) && d->ldp < (1L << 31) && d->ldd < (1L << 31);
-  if (dyn) IVH_REQUIRE(fits, "gemm_fp8: device-side row counts: every operand / output must stay below 2 GiB (32-bit descriptor offsets)");
-  if (!fits) return 1;
-  p.A = d->A; p.B = d->B; p.lda = (int)d->lda; p.ldb = (int)d->ldb; p.M = d->M; p.N = d->N; p.K = d->K;
-  p.C = d->C; p.ldc = (int)d->ldc; p.c_fp32 = 0; p.bias = d->bias; p.act = d->act;
-  p.preact = d->preact; p.ldp = (int)d->ldp; p.dact_in = d->dact_in; p.ldd = (int)d->ldd;
-  p.alpha = d->alpha; p.tiles_m = (d->M + G2_BM - 1) / G2_BM; p.tiles_n = (d->N + G2_BN - 1) / G2_BN;
-  p.batch = 1; p.a_bytes = a_bytes; p.b_bytes = b_bytes;
-  p.bias_bytes = d->bias ? (long)d->N * 4 : 0;
-  p.scale_a = scale_a; p.scale_b = scale_b; p.scale_b_vec = scale_b_vec;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) n_cu = 256;
-    else n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
+  g2_fill(p, d, e, fp8);
+  *key = g2_key(d, fp8, 0, 0, dyn);                       // (e4m3: x dact_in was accepted with act = 3 / 4 only: EPI is never 1)
+  const long total = p.total_tiles;
+  const bool ws_ok = split_ok && d->split_ws && ((uintptr_t)d->split_ws % 16) == 0;
+  G2Split sp;
+  const int64_t need = (ws_ok && !(dyn && total < cap)) ? g2_split_need(d, fp8, cap, &sp) : 0;
+  if (dyn && !fp8) {                                      // device-side row counts (DYN kernels): no host tail split, no half-width tiles
+    IVH_REQUIRE(p.batch == 1 && !g_g2_dbg && !g_g2_sched, "gemm256: device-side row counts (m_dev / k_dev) are built for single, unbatched problems");
+    IVH_REQUIRE(!(d->m_dev && d->k_dev), "gemm256: m_dev and k_dev are mutually exclusive");
+    IVH_REQUIRE(!d->m_dev || d->a_kc, "gemm256: m_dev counts the rows of a K-contiguous A (forward / dgrad launches)");
+    IVH_REQUIRE(!d->k_dev || (!d->a_kc && !d->b_kc && key->epi == 0), "gemm256: k_dev counts the rows of rows-contiguous operands (weight gradients, plain epilogue)");
+    IVH_REQUIRE(g2_find(*key), "gemm256: m_dev with the erf-recomputing dgrad epilogue (act = 1) is not built; use act = 3 / 4");
   }
-  const long total = (long)p.tiles_m * p.tiles_n;
-  p.total_tiles = (int)total; p.nprob = 0; p.stagger = 0; p.debug_skip_stores = 0; p.debug_stamps = nullptr;
-  const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
-  hipStream_t s = (hipStream_t)stream;
-  const int epi = g2_epi(d);                              // (x dact_in was accepted with act = 3 / 4 only: never 1)
-  if (dyn) {                                              // device-side row counts (DYN kernels): whole tiles, no tail split
-    p.m_dev = d->m_dev; p.k_dev = d->k_dev;
-    p.colsum_part = (epi == 3) ? d->colsum_part : nullptr;
-    p.split_main = p.total_tiles;
-    dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
-    if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
-    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true, false, false, true>), grid, block, 0, s, p);
-    return ivh_host::check_launch("gemm256_fp8 (device-side row count)") ? -1 : 0;
+  if (need > 0 && d->split_ws_bytes >= need) {            // tail tiles cut into K slices (SPLIT kernels); DYN: planned on the device (long K,
+    key->split = 1;                                       // workspace for the largest plan supplied)
+    p.split_cnt = reinterpret_cast<unsigned*>(d->split_ws);
+    p.split_ws = reinterpret_cast<float*>(reinterpret_cast<char*>(d->split_ws) + 4096);
+    p.split_ws_bytes = need - 4096;
+    if (!dyn) { p.split_main = sp.main_tiles; p.split_s = sp.S; p.split_nk2 = sp.per; p.total_tiles = sp.main_tiles + sp.tail * sp.S; }
+  } else if (!dyn && !fp8 && g2_half_flavour(d) && !g_g2_dbg && !g_g2_sched && g_g2_stagger <= 0 &&
+             g2_half_plan(d->M, d->N, cap, &p.tiles_nf, &p.half_begin, &p.half_split, &p.total_tiles)) {   // half-width tiles (HALF kernels)
+    key->half = 1; p.half_interleave = g_g2_half == 1 ? 1 : (g_g2_half == 3 ? 2 : 0);
+  } else if (!dyn && !fp8 && key->epi == 0 && d->a_kc && d->b_kc) {   // the measurement variants exist for the plain NT kernel; an ablation beats the schedule
+    key->dbg = g_g2_dbg; key->sched = g_g2_dbg ? 0 : g_g2_sched;
   }
-  if (g2_apply_split(d, 1, p, cap, s)) {
-    dim3 grid((unsigned)(p.total_tiles < cap ? p.total_tiles : cap), 1, 1), block(512);
-    if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true, true>), grid, block, 0, s, p);
-    else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true, true>), grid, block, 0, s, p);
-    else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true, true>), grid, block, 0, s, p);
-    else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true, true>), grid, block, 0, s, p);
-    return ivh_host::check_launch("gemm256_fp8 (tail split)") ? -1 : 0;
-  }
-  dim3 grid((unsigned)(total < cap ? total : cap), 1, 1), block(512);
-  if (epi == 0) hipLaunchKernelGGL((gemm256_kernel<true, true, 0, false, 0, 0, true>), grid, block, 0, s, p);
-  else if (epi == 2) hipLaunchKernelGGL((gemm256_kernel<true, true, 2, false, 0, 0, true>), grid, block, 0, s, p);
-  else if (epi == 4) hipLaunchKernelGGL((gemm256_kernel<true, true, 4, false, 0, 0, true>), grid, block, 0, s, p);
-  else hipLaunchKernelGGL((gemm256_kernel<true, true, 3, false, 0, 0, true>), grid, block, 0, s, p);
-  return ivh_host::check_launch("gemm256_fp8") ? -1 : 0;
+  return 0;
 }
 
+// route, clear the split counters, launch: both single-problem launchers
+static int g2_run(const ivh_gemm_desc* d, int fp8, int force, const float* scale_a, const float* scale_b, int scale_b_vec, hipStream_t s) {
+  static const char* const mode[5] = {"", " (half-width tiles)", " (tail split)", " (device-side row count)", " (device-side row count, tail split)"};
+  const long cap = g2_cap();
+  ivh::Gemm256Params p{};
+  G2Key k;
+  int rc = g2_route(d, fp8, force, cap, 1, p, &k);
+  if (rc) return rc;
+  if (k.split && hipMemsetAsync(d->split_ws, 0, 4096, s) != hipSuccess && (rc = g2_route(d, fp8, force, cap, 0, p, &k)) != 0) return rc;
+  p.scale_a = scale_a; p.scale_b = scale_b; p.scale_b_vec = scale_b_vec;
+  char what[64];
+  snprintf(what, sizeof(what), "gemm256_%s%s", fp8 ? "fp8" : "bf16", mode[k.dyn ? 3 + k.split : (k.split ? 2 : k.half)]);
+  return g2_launch(k, p.total_tiles < cap ? p.total_tiles : cap, s, p, what);
+}
 
-// Grouped launch: n <= 32 problems with the same K and operand layouts, plain bf16 output (no bias / activation / batch), one
-// persistent kernel over the concatenated tile lists.  Returns 1 if this set cannot be grouped (the caller launches them one
-// by one), 0 when enqueued, < 0 on error.
-extern "C" int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* stream) {
+// Launcher used by ivh_gemm_bf16 (gemm.hip) when the 256^2 kernel is selected.  Arguments were validated there.
+extern "C" int ivh_gemm256_launch(const ivh_gemm_desc* d, void* stream) { return g2_run(d, 0, 0, nullptr, nullptr, 0, (hipStream_t)stream); }
+// e4m3 operands: 1 when the problem is not for this kernel (see g2_route), 0 when enqueued, -1 on error
+extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream) {
+  const int rc = g2_run(d, 1, force, scale_a, scale_b, scale_b_vec, (hipStream_t)stream);
+  return rc < 0 ? -1 : rc;
+}
+
+// Grouped launch: n <= 32 problems with the same operand layouts, plain bf16 output (no bias / activation / batch), one persistent kernel over
+// the concatenated tile lists.  Fills p and the key; returns 1 if this set cannot be grouped, < 0 on error.
+static int g2_route_grouped(const ivh_gemm_desc* d, int n, ivh::Gemm256Params& p, G2Key* key) {
   using namespace ivh;
   if (n < 2 || n > 32) return 1;
   for (int i = 0; i < n; ++i) {
@@ -1581,23 +1525,20 @@ extern "C" int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* s
     if (q.bias || q.act || q.preact || q.dact_in || q.c_fp32 || q.alpha != 1.0f || (q.batch > 1)) return 1;
     if (!ivh_gemm256_supported(&q)) return 1;
   }
-  Gemm256Params p{};
-  int kmax = 0;
-  for (int i = 0; i < n; ++i) kmax = d[i].K > kmax ? d[i].K : kmax;
-  p.K = kmax; p.alpha = 1.0f; p.batch = 1; p.nprob = n;                  // problems may differ in K (per-problem K: the DYN grouped kernel)
-  const long lim = (1L << 31) - (1L << 24);
+  p.alpha = 1.0f; p.batch = 1; p.nprob = n;              // problems may differ in K (per-problem K: the DYN grouped kernel); p.K is the largest
   int tile = 0;
   bool dyn = false;                                      // some problem's contraction length lives in device memory (ivh_gemm_desc.k_dev)
   for (int i = 0; i < n; ++i) {
     const ivh_gemm_desc& q = d[i];
+    const G2Extents e = g2_extents(&q, 2);
     G2Prob& g = p.prob[i];
     g.A = q.A; g.B = q.B; g.C = q.C; g.lda = (int)q.lda; g.ldb = (int)q.ldb; g.ldc = (int)q.ldc; g.M = q.M; g.N = q.N;
-    g.a_bytes = (((long)q.K - 1) * q.lda + q.M) * 2; g.b_bytes = (((long)q.K - 1) * q.ldb + q.N) * 2;
-    g.c_bytes = (((long)q.M - 1) * q.ldc + q.N) * 2;
-    if (g.a_bytes >= lim || g.b_bytes >= lim || g.c_bytes >= lim) return 1;          // too large for 32-bit offsets: launched one by one
+    g.a_bytes = e.a; g.b_bytes = e.b; g.c_bytes = e.c;
+    if (!e.operands_fit || !e.outputs_fit) return 1;     // too large for 32-bit offsets: launched one by one
     IVH_REQUIRE(q.lda < (1L << 31) && q.ldb < (1L << 31) && q.ldc < (1L << 31), "gemm256 grouped: leading dimension does not fit 31 bits");
     g.tiles_m = (q.M + G2_BM - 1) / G2_BM; g.tiles_n = (q.N + G2_BN - 1) / G2_BN; g.tile_begin = tile;
     g.k_dev = q.k_dev; g.K = q.K; dyn = dyn || q.k_dev != nullptr || q.K != d[0].K;
+    p.K = q.K > p.K ? q.K : p.K;
     if (q.m_dev) return 1;                               // (a row count on the output side: not a weight gradient)
     tile += g.tiles_m * g.tiles_n;
   }
@@ -1606,17 +1547,27 @@ extern "C" int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* s
   p.M = d[0].M; p.N = d[0].N; p.tiles_m = p.prob[0].tiles_m; p.tiles_n = p.prob[0].tiles_n;
   p.a_bytes = p.prob[0].a_bytes; p.b_bytes = p.prob[0].b_bytes; p.c_bytes = p.prob[0].c_bytes;
   p.total_tiles = tile;
-  p.stagger = 0; p.debug_skip_stores = g_g2_skip_stores; p.debug_stamps = nullptr;
-  static int n_cu = 0;
-  if (n_cu == 0) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) n_cu = 256;
-    else n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  const long cap = g_g2_max_wg > 0 ? g_g2_max_wg : n_cu;
-  dim3 grid((unsigned)(tile < cap ? tile : cap), 1, 1), block(512);
-  if (dyn) hipLaunchKernelGGL((gemm256_kernel<false, false, 0, true, 0, 0, false, false, false, true>), grid, block, 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL((gemm256_kernel<false, false, 0, true>), grid, block, 0, (hipStream_t)stream, p);
-  return ivh_host::check_launch("gemm256_grouped");
+  p.debug_skip_stores = g_g2_skip_stores;
+  *key = G2Key{0, 0, 0, 1, 0, 0, 0, 0, 0, dyn};
+  return 0;
+}
+// Returns 1 if this set cannot be grouped (the caller launches them one by one), 0 when enqueued, < 0 on error.
+extern "C" int ivh_gemm256_grouped_launch(const ivh_gemm_desc* d, int n, void* stream) {
+  ivh::Gemm256Params p{};
+  G2Key k;
+  const int rc = g2_route_grouped(d, n, p, &k);
+  if (rc) return rc;
+  const long cap = g2_cap();
+  return g2_launch(k, p.total_tiles < cap ? p.total_tiles : cap, (hipStream_t)stream, p, "gemm256_grouped");
+}
+
+// the key the launchers would pick (internvideo_hip_debug.h): mode 0 = bf16, 1 = e4m3 (size test on), n >= 2 = grouped launch of d[0 .. n)
+extern "C" int ivh_gemm256_debug_route(const ivh_gemm_desc* d, int mode, int cap, int* out10) {
+  if (!d || !out10) return 0;
+  ivh::Gemm256Params p{};
+  G2Key k;
+  if ((mode >= 2 ? g2_route_grouped(d, mode, p, &k) : g2_route(d, mode, 0, cap > 0 ? cap : g2_cap(), 1, p, &k)) != 0) return 0;
+  const int v[10] = {k.a_kc, k.b_kc, k.epi, k.grouped, k.dbg, k.sched, k.fp8, k.split, k.half, k.dyn};
+  memcpy(out10, v, sizeof(v));
+  return 1;
 }

@@ -445,13 +445,11 @@ extern "C" int ivh_fp8_quantize_weight(const uint16_t* w, int64_t ld, int N, int
   return ivh_host::check_launch("fp8_quantize_weight");
 }
 
-extern "C" int ivh_gemm256_fp8_launch(const ivh_gemm_desc* d, const float* scale_a, const float* scale_b, int scale_b_vec, int force, void* stream);   // gemm256.hip
 // 0 = per problem (256^2 when it applies), 1 = always the 128^2 kernel (A/B, tests), 2 = always the 256^2 kernel where the layout allows (tests:
 // the reference launch of a bitwise comparison with a count-carrying one must run on the same kernel at fixture sizes)
 static int g_f8_kernel = 0;
 extern "C" int ivh_set_gemm_fp8_kernel(int choice) { g_f8_kernel = (choice == 1 || choice == 2) ? choice : 0; return 0; }
 
-extern "C" int64_t ivh_gemm256_split_ws_bytes(const ivh_gemm_desc* d, int fp8);      // gemm256.hip
 // bytes of d->split_ws with which ivh_gemm_fp8 would cut the tiles of a mostly empty last round into K slices (0 = no use)
 extern "C" int64_t ivh_gemm_fp8_split_workspace(const ivh_gemm_desc* d) {
   if (!d || g_f8_kernel == 1 || !d->a_kc || !d->b_kc || d->m_dev || d->k_dev) return 0;      // (count-carrying launches run whole tiles only)
