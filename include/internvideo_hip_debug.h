@@ -32,7 +32,18 @@ int ivh_gemm256_debug_half(int on);
  * choice (size test on for a count-free descriptor), n >= 2 = the grouped launch of d[0 .. n).  Returns 1, or 0 when the launcher would refuse
  * the descriptor or hand it over to the 128x128 kernel (out10 is then not written). */
 int ivh_gemm256_debug_route(const ivh_gemm_desc* d, int mode, int cap, int* out10);
-int ivh_gemm256_debug_ablate(int mode);         /* K-loop ablation of the plain NT kernel: 0 off, 1 no MFMA, 2 no LDS-DMA, 3 no fragment reads (garbage results) */
+/* Host logic only (no device needed, nothing dereferenced): the kernel one of the six ivh_rmsnorm_add_* entry points would launch, chosen by the
+ * route function the entry points themselves call (norms.hip).  bwd: 0 forward, 1 backward.  flavour: 0 = ivh_rmsnorm_add_{fwd,bwd}, 1 = *_bf16res,
+ * 2 / 3 = *_skip with res_bf16 = 0 / 1.  `set`: bit i = the entry's i-th POINTER argument (stream excluded) is non-NULL, counted over the _skip
+ * entry's argument list -- forward: res_in, branch, gamma, rowscale, w, res_out, y, rstd, branch_slot, y_slot; backward: dy, dres_out, res_out,
+ * rstd, w, branch, gamma, rowscale, dres_in, dbranch, dw_part, dgamma_part, dbias_part, dres_extra, y_slot, branch_slot.  Bits of arguments the
+ * flavour's entry does not take (the slot maps outside _skip, dres_extra on flavour 0) are ignored.
+ * Returns 1 and out9 = {b16, nch_t, wpr, rows, extra, skip, res_bf16, grid, shmem_bytes}: b16 = 0 is rmsnorm_add_{fwd,bwd}_kernel<nch_t, wpr,
+ * float | bf16_t by res_bf16, skip> (rows = 0), b16 = 1 is rmsnorm_add_bwd_b16_kernel<nch_t, rows, extra, skip> (wpr = 0); extra = dres_extra is
+ * passed; grid workgroups of 256 threads with shmem_bytes of dynamic LDS.  Returns 0, with ivh_last_error set and out9 untouched, when the
+ * entry point would refuse the call. */
+int ivh_rmsnorm_add_debug_route(int bwd, int flavour, unsigned set, int M, int D, int rows_per_sample, int* out9);
+int ivh_gemm256_debug_ablate(int mode);        /* K-loop ablation of the plain NT kernel: 0 off, 1 no MFMA, 2 no LDS-DMA, 3 no fragment reads (garbage results) */
 
 /* probes used by tests/test_hw_probe.py to pin the hardware semantics the kernels rely on */
 int ivh_probe_tr16(const uint16_t* in_4x16x4, uint16_t* out_64x4, void* stream);

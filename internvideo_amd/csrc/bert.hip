@@ -319,17 +319,8 @@ __global__ __launch_bounds__(256) void ce_rows_kernel(const TX* x, int ld, int V
 using namespace ivh;
 using namespace ivh::bert;
 
-static inline int nch_for(int C) { return (C / 8 + 63) / 64; }
-static inline int row_grid(int M, int cap) { int g = (M + 3) / 4; return g < cap ? (g < 1 ? 1 : g) : cap; }
-
-#define IVH_BERT_DISPATCH(nch, KERNEL, EMBED, grid, block, shmem, s, ...)                                    \
-  switch (nch) {                                                                                             \
-    case 1: hipLaunchKernelGGL((KERNEL<1, EMBED>), grid, block, shmem, s, __VA_ARGS__); break;               \
-    case 2: hipLaunchKernelGGL((KERNEL<2, EMBED>), grid, block, shmem, s, __VA_ARGS__); break;               \
-    case 3: hipLaunchKernelGGL((KERNEL<3, EMBED>), grid, block, shmem, s, __VA_ARGS__); break;               \
-    case 4: hipLaunchKernelGGL((KERNEL<4, EMBED>), grid, block, shmem, s, __VA_ARGS__); break;               \
-    default: ivh_host::set_error("row width %d not supported by the text-tower kernels (max 2048)", (nch) * 512); return -1; \
-  }
+using namespace ivh_host;
+static const char* const TOO_WIDE = "row width %d not supported by the text-tower kernels (max 2048)";
 
 static int make_drop(float p, uint32_t seed, DropCfg* d) {
   IVH_REQUIRE(p >= 0.0f && p < 1.0f, "dropout: p = %f outside [0, 1)", (double)p);
@@ -349,8 +340,9 @@ extern "C" int ivh_add_layernorm_fwd(const uint16_t* a, const uint16_t* r, int a
   DropCfg dc;
   if (make_drop(drop_p, seed, &dc)) return -1;
   RowSrc src{a, r, nullptr, nullptr, nullptr, nullptr, 1, act, dc};
-  IVH_BERT_DISPATCH(nch_for(C), ln_fwd_kernel, false, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream, src, w, b, eps, M, C, y, stats);
-  return ivh_host::check_launch("add_layernorm_fwd");
+  return launch_row_width("add_layernorm_fwd", nch_for(C), 4, TOO_WIDE, [&](auto N, auto) {
+    hipLaunchKernelGGL((ln_fwd_kernel<N(), false>), dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream, src, w, b, eps, M, C, y, stats);
+  });
 }
 
 extern "C" int ivh_add_layernorm_bwd(const uint16_t* a, const uint16_t* r, int act, const float* w, const float* stats, const uint16_t* dy,
@@ -364,9 +356,10 @@ extern "C" int ivh_add_layernorm_bwd(const uint16_t* a, const uint16_t* r, int a
   if (make_drop(drop_p, seed, &dc)) return -1;
   RowSrc src{a, r, nullptr, nullptr, nullptr, nullptr, 1, act, dc};
   const int grid = ivh_norm_bwd_parts(M);
-  IVH_BERT_DISPATCH(nch_for(C), ln_bwd_kernel, false, dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream, src, w, stats,
-                    dy, dy2, M, C, dx, dx_a, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0, dw_part, db_part);
-  return ivh_host::check_launch("add_layernorm_bwd");
+  return launch_row_width("add_layernorm_bwd", nch_for(C), 4, TOO_WIDE, [&](auto N, auto) {
+    hipLaunchKernelGGL((ln_bwd_kernel<N(), false>), dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream, src, w, stats,
+                       dy, dy2, M, C, dx, dx_a, (float*)nullptr, (float*)nullptr, (float*)nullptr, 0, dw_part, db_part);
+  });
 }
 
 extern "C" int ivh_bert_embed_fwd(const int* ids, int M, int L, const float* word, const float* pos, const float* type, const float* w,
@@ -376,8 +369,9 @@ extern "C" int ivh_bert_embed_fwd(const int* ids, int M, int L, const float* wor
   DropCfg dc;
   if (make_drop(drop_p, seed, &dc)) return -1;
   RowSrc src{nullptr, nullptr, ids, word, pos, type, L, 0, dc};
-  IVH_BERT_DISPATCH(nch_for(C), ln_fwd_kernel, true, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream, src, w, b, eps, M, C, y, stats);
-  return ivh_host::check_launch("bert_embed_fwd");
+  return launch_row_width("bert_embed_fwd", nch_for(C), 4, TOO_WIDE, [&](auto N, auto) {
+    hipLaunchKernelGGL((ln_fwd_kernel<N(), true>), dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream, src, w, b, eps, M, C, y, stats);
+  });
 }
 
 extern "C" int ivh_bert_embed_bwd(const int* ids, int M, int L, const float* word, const float* pos, const float* type, const float* w,
@@ -389,9 +383,10 @@ extern "C" int ivh_bert_embed_bwd(const int* ids, int M, int L, const float* wor
   if (make_drop(drop_p, seed, &dc)) return -1;
   RowSrc src{nullptr, nullptr, ids, word, pos, type, L, 0, dc};
   const int grid = ivh_norm_bwd_parts(M);
-  IVH_BERT_DISPATCH(nch_for(C), ln_bwd_kernel, true, dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream, src, w, stats,
-                    dy, (const bf16_t*)nullptr, M, C, (bf16_t*)nullptr, (bf16_t*)nullptr, dword, dpos, dtype, pad_id, dw_part, db_part);
-  return ivh_host::check_launch("bert_embed_bwd");
+  return launch_row_width("bert_embed_bwd", nch_for(C), 4, TOO_WIDE, [&](auto N, auto) {
+    hipLaunchKernelGGL((ln_bwd_kernel<N(), true>), dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream, src, w, stats,
+                       dy, (const bf16_t*)nullptr, M, C, (bf16_t*)nullptr, (bf16_t*)nullptr, dword, dpos, dtype, pad_id, dw_part, db_part);
+  });
 }
 
 extern "C" int ivh_ce_rows(const void* logits, int logits_fp32, int ld, int M, int V, const int* labels, int ignore_index, float dscale,

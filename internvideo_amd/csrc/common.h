@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace ivh {
 
@@ -143,6 +144,33 @@ namespace ivh_host {
 void set_error(const char* fmt, ...);
 int check_launch(const char* what);
 const unsigned* dropout_epoch();          // device pointer registered with ivh_set_dropout_epoch, or NULL
+
+// ---- launch geometry of the row kernels (norms.hip, bert.hip): a row of D elements is D / 8 chunks of 16 bytes -----------------------
+inline int nch_for(int D) { return (D / 8 + 63) / 64; }                   // chunks per lane when ONE wave holds the row
+inline int row_grid(int M, int cap) { int g = (M + 3) / 4; return g < cap ? (g < 1 ? 1 : g) : cap; }   // four rows per workgroup and trip
+template <int V> using int_c = std::integral_constant<int, V>;
+// The width map, the only one: nch = nch_for(D) -> the <NCH, WPR> a row kernel is instantiated with.  Up to 4 chunks a wave per row
+// (<nch, 1>), 5 .. 8 the four waves of a workgroup share the row (<2, 4>).  fn(N, W) receives them as int_c values (N() and W() are constant
+// expressions); false, with fn not called, for nch outside 1 .. max_nch: the caller owns the message.
+template <typename F>
+inline bool for_row_width(int nch, int max_nch, F&& fn) {
+  switch (nch <= max_nch ? nch : 0) {
+    case 1: fn(int_c<1>{}, int_c<1>{}); return true;
+    case 2: fn(int_c<2>{}, int_c<1>{}); return true;
+    case 3: fn(int_c<3>{}, int_c<1>{}); return true;
+    case 4: fn(int_c<4>{}, int_c<1>{}); return true;
+    case 5: case 6: case 7: case 8: fn(int_c<2>{}, int_c<4>{}); return true;
+    default: return false;
+  }
+}
+// one launch through the width map: fn(N, W) launches, `what` names it to check_launch; `too_wide` is the caller's message for a row the
+// map has no kernel for (one %d: the width in elements)
+template <typename F>
+inline int launch_row_width(const char* what, int nch, int max_nch, const char* too_wide, F&& fn) {
+  if (for_row_width(nch, max_nch, fn)) return check_launch(what);
+  set_error(too_wide, nch * 512);
+  return -1;
+}
 }  // namespace ivh_host
 
 // ---- internals of the 256x256 GEMM (gemm256.hip) that gemm.hip / gemm_fp8.hip route through; not part of the C ABI headers --------

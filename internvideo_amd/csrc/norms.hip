@@ -1317,14 +1317,11 @@ __global__ __launch_bounds__(256) void sum_rows_kernel(const float* __restrict__
   if (threadIdx.x == 0) out[0] = red[0] * scale;
 }
 
-static inline int nch_for(int D) { return (D / 8 + 63) / 64; }
-static inline int row_grid(int M, int cap) { int g = (M + 3) / 4; return g < cap ? (g < 1 ? 1 : g) : cap; }
 // workgroups (= partial-sum rows) of the backward row kernels.  IVH_BWD_PARTS overrides it for occupancy experiments (tools/bench_rows.py)
 static int bwd_parts_cap() {
   static const int v = [] { const char* e = getenv("IVH_BWD_PARTS"); const int n = e ? atoi(e) : 0; return n >= 64 && n <= 8192 ? n : 512; }();
   return v;
 }
-#define BWD_PARTS_CAP bwd_parts_cap()
 // rows per workgroup and trip of the bf16-stream backward (rmsnorm_add_bwd_b16_kernel): 1 by default -- measured on M = 53376, D = 1408
 // (profiles/r3_rows_bf16_stream_sweep.jsonl): generic kernel 247 us, 1 row 174 us, 2 rows 182 us, 4 rows 188 us at 512 workgroups; more
 // workgroups are slower for every shape.  IVH_BWD_ROWS = 1 / 2 / 4 selects, 0 = the generic kernel
@@ -1335,52 +1332,142 @@ static int bwd_rows() {
 
 }  // namespace ivh
 
-#define IVH_DISPATCH_NCH(nch, KERNEL, grid, block, shmem, s, ...)                                   \
-  switch (nch) {                                                                                    \
-    case 1: hipLaunchKernelGGL((KERNEL<1>), grid, block, shmem, s, __VA_ARGS__); break;             \
-    case 2: hipLaunchKernelGGL((KERNEL<2>), grid, block, shmem, s, __VA_ARGS__); break;             \
-    case 3: hipLaunchKernelGGL((KERNEL<3>), grid, block, shmem, s, __VA_ARGS__); break;             \
-    case 4: hipLaunchKernelGGL((KERNEL<4>), grid, block, shmem, s, __VA_ARGS__); break;             \
-    case 5: case 6: case 7: case 8: hipLaunchKernelGGL((KERNEL<2, 4>), grid, block, shmem, s, __VA_ARGS__); break; \
-    default: ivh_host::set_error("row width %d not supported (max 4096)", (nch) * 512); return -1;  \
-  }
-
-#define IVH_DISPATCH_NCH_R(nch, KERNEL, TR, grid, block, shmem, s, ...)                             \
-  switch (nch) {                                                                                    \
-    case 1: hipLaunchKernelGGL((KERNEL<1, 1, TR>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 2: hipLaunchKernelGGL((KERNEL<2, 1, TR>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 3: hipLaunchKernelGGL((KERNEL<3, 1, TR>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 4: hipLaunchKernelGGL((KERNEL<4, 1, TR>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 5: case 6: case 7: case 8: hipLaunchKernelGGL((KERNEL<2, 4, TR>), grid, block, shmem, s, __VA_ARGS__); break; \
-    default: ivh_host::set_error("row width %d not supported (max 4096)", (nch) * 512); return -1;  \
-  }
-
 using namespace ivh;
+using namespace ivh_host;       // nch_for, row_grid, for_row_width / launch_row_width: the width map of every row kernel (common.h)
+static const char* const TOO_WIDE = "row width %d not supported (max 4096)";
+template <typename F>
+static void for_bool(bool b, F&& fn) { if (b) fn(std::true_type{}); else fn(std::false_type{}); }
+
+// ---- rmsnorm_add: three entry points per direction (fp32 stream, bf16 stream, _skip), ONE route and ONE launcher per direction ----------
+// The arguments of one launch.  Tensors of the residual stream are untyped (res_bf16 says which type); the slot maps belong to the _skip
+// entries and dres_extra to the bf16 stream: NULL elsewhere.
+struct RmsAddFwd {
+  int skip, res_bf16;
+  const void* res_in; const bf16_t* branch; const float *gamma, *rowscale; int rows_per_sample; const float* w; float eps; int M, D;
+  void* res_out; bf16_t* y; float* rstd; const int32_t *branch_slot, *y_slot;
+};
+struct RmsAddBwd {
+  int skip, res_bf16;
+  const bf16_t* dy; const void *dres_out, *res_out; const float *rstd, *w; const bf16_t* branch; const float *gamma, *rowscale;
+  int rows_per_sample, M, D; void* dres_in; bf16_t* dbranch; float *dw_part, *dgamma_part, *dbias_part; const void* dres_extra;
+  const int32_t *y_slot, *branch_slot;
+};
+// The kernel a launch runs (ivh_rmsnorm_add_debug_route shows these nine fields).  b16 = 0: rmsnorm_add_{fwd,bwd}_kernel<nch_t, wpr, TR, skip>
+// (rows = 0); b16 = 1: rmsnorm_add_bwd_b16_kernel<nch_t, rows, extra, skip> (wpr = 0: its four waves always share a row).
+struct RmsAddRoute { int b16, nch_t, wpr, rows, extra, skip, res_bf16, grid, shmem_bytes; };
+
+// the generic kernels' <NCH, WPR>: what for_row_width hands the launcher for the same D
+static int route_generic_width(int D, RmsAddRoute* r) {
+  const int nch = nch_for(D);
+  IVH_REQUIRE(for_row_width(nch, 8, [&](auto N, auto W) { r->nch_t = N(); r->wpr = W(); }), TOO_WIDE, nch * 512);
+  return 0;
+}
+
+// The routes launch nothing and look at which pointers are set, never behind them.  `entry`: the calling entry point, for the messages.
+static int route_rmsnorm_add_fwd(const char* entry, const RmsAddFwd& a, RmsAddRoute* r) {
+  IVH_REQUIRE(a.M > 0 && a.D > 0 && a.D % 8 == 0, "%s: bad shape M=%d D=%d", entry, a.M, a.D);
+  IVH_REQUIRE(a.res_in || a.branch, "%s: need res_in or branch", entry);
+  IVH_REQUIRE(!a.y || a.w, "%s: y requested without weight", entry);
+  if (a.skip) {
+    IVH_REQUIRE(a.rows_per_sample > 0 && a.M % a.rows_per_sample == 0, "%s: M=%d must be whole samples of %d rows", entry, a.M, a.rows_per_sample);
+    IVH_REQUIRE(a.res_in || !a.branch_slot, "%s: a compacted branch needs the stream it is added to", entry);
+  } else {
+    IVH_REQUIRE(!a.rowscale || a.rows_per_sample > 0, "%s: rows_per_sample must be > 0", entry);
+  }
+  *r = RmsAddRoute{0, 0, 0, 0, 0, a.skip, a.res_bf16, row_grid(a.M, 8192), 0};
+  return route_generic_width(a.D, r);
+}
+
+static int route_rmsnorm_add_bwd(const char* entry, const RmsAddBwd& a, RmsAddRoute* r) {
+  IVH_REQUIRE(a.M > 0 && a.D > 0 && a.D % 8 == 0, "%s: bad shape M=%d D=%d", entry, a.M, a.D);
+  if (a.skip) {
+    IVH_REQUIRE(a.rows_per_sample > 0 && a.M % a.rows_per_sample == 0, "%s: M=%d must be whole samples of %d rows", entry, a.M, a.rows_per_sample);
+    IVH_REQUIRE(!a.dres_extra || (a.dres_out && a.res_bf16), "%s: dres_extra joins a bf16 dres_out", entry);
+  } else {
+    IVH_REQUIRE(!a.dres_extra || a.dres_out, "%s: dres_extra joins dres_out (pass it as dres_out when it is the only gradient)", entry);
+  }
+  IVH_REQUIRE(!a.dbias_part || a.dbranch, "%s: dbias_part is the column sum of dbranch", entry);
+  IVH_REQUIRE(a.dy || a.dres_out, "%s: need dy or dres_out", entry);
+  IVH_REQUIRE(!a.dy || (a.res_out && a.rstd && a.w && a.dw_part), "%s: dy needs res_out, rstd, w, dw_part", entry);
+  *r = RmsAddRoute{0, 0, 0, 0, a.dres_extra != nullptr, a.skip, a.res_bf16, row_grid(a.M, bwd_parts_cap()), 0};
+  // a block's interior on a bf16 stream: the bytes-in-flight kernel (its buffer descriptors hold M * D * 2 bytes: below 2 GiB)
+  const bool interior = a.dy && a.dres_out && a.res_out && a.branch && a.gamma && a.dres_in && a.dbranch && a.dw_part && a.dgamma_part && a.dbias_part;
+  if (a.res_bf16 && interior && nch_for(a.D) <= 8 && bwd_rows() > 0 && (long)a.M * a.D * 2 < (1L << 31)) {
+    r->b16 = 1;
+    r->nch_t = (a.D / 8 + 255) / 256;                      // 16-byte chunks per lane when four waves share a row: 1 up to D = 2048, else 2
+    const int want = (r->extra || r->skip) ? 1 : bwd_rows();   // a tapped block (10 of the 1B step's 79 launches) and the _skip entry: one row per trip
+    r->rows = (want >= 4 && r->nch_t == 1) ? 4 : (want >= 2 ? 2 : 1);
+    return 0;
+  }
+  if (route_generic_width(a.D, r)) return -1;
+  r->shmem_bytes = 4 * a.D * (int)sizeof(float);
+  return 0;
+}
+
+static void launch_rmsnorm_add_fwd(const RmsAddRoute& r, const RmsAddFwd& a, void* stream) {
+  for_bool(r.res_bf16, [&](auto B16) { for_bool(r.skip, [&](auto SK) {
+    using TR = std::conditional_t<decltype(B16)::value, bf16_t, float>;
+    constexpr bool SKIP = decltype(SK)::value;
+    for_row_width(nch_for(a.D), 8, [&](auto N, auto W) {
+      hipLaunchKernelGGL((rmsnorm_add_fwd_kernel<N(), W(), TR, SKIP>), dim3(r.grid), dim3(256), r.shmem_bytes, (hipStream_t)stream, (const TR*)a.res_in, a.branch,
+                         a.gamma, a.rowscale, a.rows_per_sample, a.w, a.eps, a.M, a.D, (TR*)a.res_out, a.y, a.rstd, a.branch_slot, a.y_slot);
+    });
+  }); });
+}
+
+template <int N, int ROWS, bool EXTRA, bool SKIP>
+static void launch_bwd_b16(const RmsAddRoute& r, const RmsAddBwd& a, void* stream) {
+  hipLaunchKernelGGL((rmsnorm_add_bwd_b16_kernel<N, ROWS, EXTRA, SKIP>), dim3(r.grid), dim3(256), 0, (hipStream_t)stream, a.dy, (const bf16_t*)a.dres_out,
+                     (const bf16_t*)a.res_out, a.rstd, a.w, a.branch, a.gamma, a.rowscale, a.rows_per_sample, a.M, a.D, (bf16_t*)a.dres_in, a.dbranch,
+                     a.dw_part, a.dgamma_part, a.dbias_part, (const bf16_t*)a.dres_extra, a.y_slot, a.branch_slot);
+}
+static void launch_rmsnorm_add_bwd(const RmsAddRoute& r, const RmsAddBwd& a, void* stream) {
+  if (r.b16) {                                             // ROWS > 1 exists without EXTRA and SKIP only, ROWS = 4 at NCH = 1 only: as the route says
+    for_bool(r.nch_t == 2, [&](auto WIDE) {
+      constexpr int N = decltype(WIDE)::value ? 2 : 1;
+      if (r.skip) for_bool(r.extra, [&](auto EX) { launch_bwd_b16<N, 1, decltype(EX)::value, true>(r, a, stream); });
+      else if (r.extra) launch_bwd_b16<N, 1, true, false>(r, a, stream);
+      else if (r.rows == 2) launch_bwd_b16<N, 2, false, false>(r, a, stream);
+      else if (r.rows == 1) launch_bwd_b16<N, 1, false, false>(r, a, stream);
+      else if constexpr (N == 1) launch_bwd_b16<1, 4, false, false>(r, a, stream);
+    });
+    return;
+  }
+  float* dwp = a.dy ? a.dw_part : nullptr;
+  for_bool(r.res_bf16, [&](auto B16) { for_bool(r.skip, [&](auto SK) {
+    using TR = std::conditional_t<decltype(B16)::value, bf16_t, float>;
+    constexpr bool SKIP = decltype(SK)::value;
+    for_row_width(nch_for(a.D), 8, [&](auto N, auto W) {
+      hipLaunchKernelGGL((rmsnorm_add_bwd_kernel<N(), W(), TR, SKIP>), dim3(r.grid), dim3(256), r.shmem_bytes, (hipStream_t)stream, a.dy, (const TR*)a.dres_out,
+                         (const TR*)a.res_out, a.rstd, a.w, a.branch, a.gamma, a.rowscale, a.rows_per_sample, a.M, a.D, (TR*)a.dres_in, a.dbranch, dwp,
+                         a.dgamma_part, a.dbias_part, (const TR*)a.dres_extra, a.y_slot, a.branch_slot);
+    });
+  }); });
+}
+
+static int run_rmsnorm_add_fwd(const char* entry, const RmsAddFwd& a, void* stream) {
+  RmsAddRoute r;
+  if (route_rmsnorm_add_fwd(entry, a, &r)) return -1;
+  launch_rmsnorm_add_fwd(r, a, stream);
+  return check_launch(entry);
+}
+static int run_rmsnorm_add_bwd(const char* entry, const RmsAddBwd& a, void* stream) {
+  RmsAddRoute r;
+  if (route_rmsnorm_add_bwd(entry, a, &r)) return -1;
+  launch_rmsnorm_add_bwd(r, a, stream);
+  return check_launch(entry);
+}
 
 extern "C" int ivh_rmsnorm_add_fwd(const float* res_in, const uint16_t* branch, const float* gamma, const float* rowscale,
                                    int rows_per_sample, const float* w, float eps, int M, int D,
                                    float* res_out, uint16_t* y, float* rstd, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_fwd: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(res_in || branch, "rmsnorm_add_fwd: need res_in or branch");
-  IVH_REQUIRE(!y || w, "rmsnorm_add_fwd: y requested without weight");
-  IVH_REQUIRE(!rowscale || rows_per_sample > 0, "rmsnorm_add_fwd: rows_per_sample must be > 0");
-  const int nch = nch_for(D);
-  IVH_DISPATCH_NCH(nch, rmsnorm_add_fwd_kernel, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                   res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, res_out, y, rstd);
-  return ivh_host::check_launch("rmsnorm_add_fwd");
+  return run_rmsnorm_add_fwd("rmsnorm_add_fwd", {0, 0, res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, res_out, y, rstd, nullptr, nullptr}, stream);
 }
 
 extern "C" int ivh_rmsnorm_add_fwd_bf16res(const uint16_t* res_in, const uint16_t* branch, const float* gamma, const float* rowscale,
                                            int rows_per_sample, const float* w, float eps, int M, int D,
                                            uint16_t* res_out, uint16_t* y, float* rstd, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_fwd_bf16res: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(res_in || branch, "rmsnorm_add_fwd_bf16res: need res_in or branch");
-  IVH_REQUIRE(!y || w, "rmsnorm_add_fwd_bf16res: y requested without weight");
-  IVH_REQUIRE(!rowscale || rows_per_sample > 0, "rmsnorm_add_fwd_bf16res: rows_per_sample must be > 0");
-  const int nch = nch_for(D);
-  IVH_DISPATCH_NCH_R(nch, rmsnorm_add_fwd_kernel, bf16_t, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                     res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, res_out, y, rstd);
-  return ivh_host::check_launch("rmsnorm_add_fwd_bf16res");
+  return run_rmsnorm_add_fwd("rmsnorm_add_fwd_bf16res", {0, 1, res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, res_out, y, rstd, nullptr, nullptr}, stream);
 }
 
 // ---- DropPath sample skipping (ABI 2) ------------------------------------------------------------------------------------------------
@@ -1390,89 +1477,29 @@ extern "C" int ivh_droppath_plan(const float* rowscale, int n_sets, int B, int r
   return ivh_host::check_launch("droppath_plan");
 }
 
-#define IVH_DISPATCH_NCH_RS(nch, KERNEL, TR, grid, block, shmem, s, ...)                            \
-  switch (nch) {                                                                                    \
-    case 1: hipLaunchKernelGGL((KERNEL<1, 1, TR, true>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 2: hipLaunchKernelGGL((KERNEL<2, 1, TR, true>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 3: hipLaunchKernelGGL((KERNEL<3, 1, TR, true>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 4: hipLaunchKernelGGL((KERNEL<4, 1, TR, true>), grid, block, shmem, s, __VA_ARGS__); break;      \
-    case 5: case 6: case 7: case 8: hipLaunchKernelGGL((KERNEL<2, 4, TR, true>), grid, block, shmem, s, __VA_ARGS__); break; \
-    default: ivh_host::set_error("row width %d not supported (max 4096)", (nch) * 512); return -1;  \
-  }
-
 extern "C" int ivh_rmsnorm_add_fwd_skip(const void* res_in, int res_bf16, const uint16_t* branch, const float* gamma, const float* rowscale,
                                         int rows_per_sample, const float* w, float eps, int M, int D,
                                         void* res_out, uint16_t* y, float* rstd, const int32_t* branch_slot, const int32_t* y_slot, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_fwd_skip: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(res_in || branch, "rmsnorm_add_fwd_skip: need res_in or branch");
-  IVH_REQUIRE(!y || w, "rmsnorm_add_fwd_skip: y requested without weight");
-  IVH_REQUIRE(rows_per_sample > 0 && M % rows_per_sample == 0, "rmsnorm_add_fwd_skip: M=%d must be whole samples of %d rows", M, rows_per_sample);
-  IVH_REQUIRE(res_in || !branch_slot, "rmsnorm_add_fwd_skip: a compacted branch needs the stream it is added to");
-  const int nch = nch_for(D);
-  if (res_bf16) {
-    IVH_DISPATCH_NCH_RS(nch, rmsnorm_add_fwd_kernel, bf16_t, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                        (const bf16_t*)res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, (bf16_t*)res_out, y, rstd, branch_slot, y_slot);
-  } else {
-    IVH_DISPATCH_NCH_RS(nch, rmsnorm_add_fwd_kernel, float, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                        (const float*)res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, (float*)res_out, y, rstd, branch_slot, y_slot);
-  }
-  return ivh_host::check_launch("rmsnorm_add_fwd_skip");
+  return run_rmsnorm_add_fwd("rmsnorm_add_fwd_skip", {1, res_bf16 != 0, res_in, branch, gamma, rowscale, rows_per_sample, w, eps, M, D, res_out, y, rstd, branch_slot, y_slot},
+                             stream);
 }
 
-extern "C" int ivh_norm_bwd_parts(int M) { return row_grid(M, BWD_PARTS_CAP); }
+extern "C" int ivh_norm_bwd_parts(int M) { return row_grid(M, bwd_parts_cap()); }
 
 extern "C" int ivh_rmsnorm_add_bwd(const uint16_t* dy, const float* dres_out, const float* res_out, const float* rstd,
                                    const float* w, const uint16_t* branch, const float* gamma, const float* rowscale,
                                    int rows_per_sample, int M, int D, float* dres_in, uint16_t* dbranch,
                                    float* dw_part, float* dgamma_part, float* dbias_part, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_bwd: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(!dbias_part || dbranch, "rmsnorm_add_bwd: dbias_part is the column sum of dbranch");
-  IVH_REQUIRE(dy || dres_out, "rmsnorm_add_bwd: need dy or dres_out");
-  IVH_REQUIRE(!dy || (res_out && rstd && w && dw_part), "rmsnorm_add_bwd: dy needs res_out, rstd, w, dw_part");
-  const int nch = nch_for(D);
-  const int grid = row_grid(M, BWD_PARTS_CAP);
-  const size_t sh = (size_t)4 * D * sizeof(float);
-  IVH_DISPATCH_NCH(nch, rmsnorm_add_bwd_kernel, dim3(grid), dim3(256), sh, (hipStream_t)stream,
-                   dy, dres_out, res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D,
-                   dres_in, dbranch, dy ? dw_part : nullptr, dgamma_part, dbias_part);
-  return ivh_host::check_launch("rmsnorm_add_bwd");
+  return run_rmsnorm_add_bwd("rmsnorm_add_bwd", {0, 0, dy, dres_out, res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch,
+                                                 dw_part, dgamma_part, dbias_part, nullptr, nullptr, nullptr}, stream);
 }
 
 extern "C" int ivh_rmsnorm_add_bwd_bf16res(const uint16_t* dy, const uint16_t* dres_out, const uint16_t* res_out, const float* rstd,
                                            const float* w, const uint16_t* branch, const float* gamma, const float* rowscale,
                                            int rows_per_sample, int M, int D, uint16_t* dres_in, uint16_t* dbranch,
                                            float* dw_part, float* dgamma_part, float* dbias_part, const uint16_t* dres_extra, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_bwd_bf16res: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(!dres_extra || dres_out, "rmsnorm_add_bwd_bf16res: dres_extra joins dres_out (pass it as dres_out when it is the only gradient)");
-  IVH_REQUIRE(!dbias_part || dbranch, "rmsnorm_add_bwd_bf16res: dbias_part is the column sum of dbranch");
-  IVH_REQUIRE(dy || dres_out, "rmsnorm_add_bwd_bf16res: need dy or dres_out");
-  IVH_REQUIRE(!dy || (res_out && rstd && w && dw_part), "rmsnorm_add_bwd_bf16res: dy needs res_out, rstd, w, dw_part");
-  const int nch = nch_for(D);
-  const int grid = row_grid(M, BWD_PARTS_CAP);
-  const size_t sh = (size_t)4 * D * sizeof(float);
-  float* dwp = dy ? dw_part : nullptr;
-  const int rows = bwd_rows();
-#define IVH_B16_BWD(N, R) hipLaunchKernelGGL((rmsnorm_add_bwd_b16_kernel<N, R>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, dres_out, \
-    res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch, dwp, dgamma_part, dbias_part)
-  const bool interior = dy && dres_out && res_out && branch && gamma && dres_in && dbranch && dw_part && dgamma_part && dbias_part;
-  if (interior && nch <= 8 && rows > 0 && (long)M * D * 2 < (1L << 31)) {     // a block's interior: the bytes-in-flight kernel
-    const int n4 = (D / 8 + 255) / 256;                    // 16-byte chunks per lane when four waves share a row: 1 up to D = 2048, else 2
-    if (dres_extra) {                                      // a tapped block (10 of the 1B step's 79 launches): one row per trip
-      if (n4 == 1) hipLaunchKernelGGL((rmsnorm_add_bwd_b16_kernel<1, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, dres_out, res_out, rstd, w,
-                                      branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch, dwp, dgamma_part, dbias_part, dres_extra);
-      else hipLaunchKernelGGL((rmsnorm_add_bwd_b16_kernel<2, 1, true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, dres_out, res_out, rstd, w,
-                              branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch, dwp, dgamma_part, dbias_part, dres_extra);
-      return ivh_host::check_launch("rmsnorm_add_bwd_bf16res");
-    }
-    if (n4 == 1) { if (rows >= 4) IVH_B16_BWD(1, 4); else if (rows >= 2) IVH_B16_BWD(1, 2); else IVH_B16_BWD(1, 1); }
-    else { if (rows >= 2) IVH_B16_BWD(2, 2); else IVH_B16_BWD(2, 1); }
-    return ivh_host::check_launch("rmsnorm_add_bwd_bf16res");
-  }
-#undef IVH_B16_BWD
-  IVH_DISPATCH_NCH_R(nch, rmsnorm_add_bwd_kernel, bf16_t, dim3(grid), dim3(256), sh, (hipStream_t)stream,
-                     dy, dres_out, res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D,
-                     dres_in, dbranch, dwp, dgamma_part, dbias_part, dres_extra);
-  return ivh_host::check_launch("rmsnorm_add_bwd_bf16res");
+  return run_rmsnorm_add_bwd("rmsnorm_add_bwd_bf16res", {0, 1, dy, dres_out, res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch,
+                                                         dw_part, dgamma_part, dbias_part, dres_extra, nullptr, nullptr}, stream);
 }
 
 extern "C" int ivh_rmsnorm_add_bwd_skip(const uint16_t* dy, const void* dres_out, int res_bf16, const void* res_out, const float* rstd,
@@ -1480,37 +1507,33 @@ extern "C" int ivh_rmsnorm_add_bwd_skip(const uint16_t* dy, const void* dres_out
                                         int rows_per_sample, int M, int D, void* dres_in, uint16_t* dbranch,
                                         float* dw_part, float* dgamma_part, float* dbias_part, const void* dres_extra,
                                         const int32_t* y_slot, const int32_t* branch_slot, void* stream) {
-  IVH_REQUIRE(M > 0 && D > 0 && D % 8 == 0, "rmsnorm_add_bwd_skip: bad shape M=%d D=%d", M, D);
-  IVH_REQUIRE(rows_per_sample > 0 && M % rows_per_sample == 0, "rmsnorm_add_bwd_skip: M=%d must be whole samples of %d rows", M, rows_per_sample);
-  IVH_REQUIRE(!dres_extra || (dres_out && res_bf16), "rmsnorm_add_bwd_skip: dres_extra joins a bf16 dres_out");
-  IVH_REQUIRE(!dbias_part || dbranch, "rmsnorm_add_bwd_skip: dbias_part is the column sum of dbranch");
-  IVH_REQUIRE(dy || dres_out, "rmsnorm_add_bwd_skip: need dy or dres_out");
-  IVH_REQUIRE(!dy || (res_out && rstd && w && dw_part), "rmsnorm_add_bwd_skip: dy needs res_out, rstd, w, dw_part");
-  const int nch = nch_for(D);
-  const int grid = row_grid(M, BWD_PARTS_CAP);
-  const size_t sh = (size_t)4 * D * sizeof(float);
-  float* dwp = dy ? dw_part : nullptr;
-  hipStream_t s = (hipStream_t)stream;
-  if (!res_bf16) {
-    IVH_DISPATCH_NCH_RS(nch, rmsnorm_add_bwd_kernel, float, dim3(grid), dim3(256), sh, s, dy, (const float*)dres_out, (const float*)res_out, rstd, w, branch,
-                        gamma, rowscale, rows_per_sample, M, D, (float*)dres_in, dbranch, dwp, dgamma_part, dbias_part, (const float*)nullptr, y_slot, branch_slot);
-    return ivh_host::check_launch("rmsnorm_add_bwd_skip");
+  return run_rmsnorm_add_bwd("rmsnorm_add_bwd_skip", {1, res_bf16 != 0, dy, dres_out, res_out, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D, dres_in, dbranch,
+                                                      dw_part, dgamma_part, dbias_part, dres_extra, y_slot, branch_slot}, stream);
+}
+
+struct RouteArg {                                          // a pointer argument of the call whose route is asked for: if present, an address nobody reads
+  bool on;
+  template <typename T> operator T*() const { return on ? reinterpret_cast<T*>(16) : nullptr; }
+};
+// Host logic only (include/internvideo_hip_debug.h): the route of the entry point `flavour` of direction `bwd` with the arguments of `set` present
+extern "C" int ivh_rmsnorm_add_debug_route(int bwd, int flavour, unsigned set, int M, int D, int rows_per_sample, int* out9) {
+  IVH_REQUIRE(flavour >= 0 && flavour <= 3 && out9, "rmsnorm_add_debug_route: bad args");
+  const int skip = flavour >= 2, res_bf16 = flavour & 1;
+  const auto p = [&](int bit, bool has = true) { return RouteArg{has && (set >> bit & 1u)}; };
+  static const char* const names[2][4] = {{"rmsnorm_add_fwd", "rmsnorm_add_fwd_bf16res", "rmsnorm_add_fwd_skip", "rmsnorm_add_fwd_skip"},
+                                          {"rmsnorm_add_bwd", "rmsnorm_add_bwd_bf16res", "rmsnorm_add_bwd_skip", "rmsnorm_add_bwd_skip"}};
+  RmsAddRoute r;
+  if (bwd) {
+    const RmsAddBwd a{skip, res_bf16, p(0), p(1), p(2), p(3), p(4), p(5), p(6), p(7), rows_per_sample, M, D, p(8), p(9), p(10), p(11), p(12),
+                      p(13, flavour != 0), p(14, skip), p(15, skip)};
+    if (route_rmsnorm_add_bwd(names[1][flavour], a, &r)) return 0;
+  } else {
+    const RmsAddFwd a{skip, res_bf16, p(0), p(1), p(2), p(3), rows_per_sample, p(4), 0.f, M, D, p(5), p(6), p(7), p(8, skip), p(9, skip)};
+    if (route_rmsnorm_add_fwd(names[0][flavour], a, &r)) return 0;
   }
-  const bf16_t* dro = (const bf16_t*)dres_out; const bf16_t* ro = (const bf16_t*)res_out; const bf16_t* ex = (const bf16_t*)dres_extra;
-  bf16_t* dri = (bf16_t*)dres_in;
-  const bool interior = dy && dres_out && res_out && branch && gamma && dres_in && dbranch && dw_part && dgamma_part && dbias_part;
-  if (interior && nch <= 8 && bwd_rows() > 0 && (long)M * D * 2 < (1L << 31)) {     // a block's interior: the bytes-in-flight kernel, one row per trip
-    const int n4 = (D / 8 + 255) / 256;
-#define IVH_B16_SKIP(N, EX) hipLaunchKernelGGL((rmsnorm_add_bwd_b16_kernel<N, 1, EX, true>), dim3(grid), dim3(256), 0, s, dy, dro, ro, rstd, w, branch, gamma, \
-    rowscale, rows_per_sample, M, D, dri, dbranch, dwp, dgamma_part, dbias_part, ex, y_slot, branch_slot)
-    if (n4 == 1) { if (ex) IVH_B16_SKIP(1, true); else IVH_B16_SKIP(1, false); }
-    else { if (ex) IVH_B16_SKIP(2, true); else IVH_B16_SKIP(2, false); }
-#undef IVH_B16_SKIP
-    return ivh_host::check_launch("rmsnorm_add_bwd_skip");
-  }
-  IVH_DISPATCH_NCH_RS(nch, rmsnorm_add_bwd_kernel, bf16_t, dim3(grid), dim3(256), sh, s, dy, dro, ro, rstd, w, branch, gamma, rowscale, rows_per_sample, M, D,
-                      dri, dbranch, dwp, dgamma_part, dbias_part, ex, y_slot, branch_slot);
-  return ivh_host::check_launch("rmsnorm_add_bwd_skip");
+  const int v[9] = {r.b16, r.nch_t, r.wpr, r.rows, r.extra, r.skip, r.res_bf16, r.grid, r.shmem_bytes};
+  for (int i = 0; i < 9; ++i) out9[i] = v[i];
+  return 1;
 }
 
 // up to 4 column reductions of the same shape in one launch (blockIdx.y picks the array): the dw / dgamma (/ db) partials that one
@@ -1559,10 +1582,9 @@ extern "C" int ivh_colsum_bf16(const uint16_t* x, int64_t ld, int M, int N, floa
 extern "C" int ivh_qk_rmsnorm_fwd_dyn(uint16_t* qkv, const float* wq, const float* wk, float eps, int M, int D,
                                       float* rstd_q, float* rstd_k, const int32_t* m_dev, void* stream) {
   IVH_REQUIRE(qkv && wq && wk && rstd_q && rstd_k && M > 0 && D % 8 == 0, "qk_rmsnorm_fwd: bad args");
-  const int nch = nch_for(D);
-  IVH_DISPATCH_NCH(nch, qk_rmsnorm_fwd_kernel, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                   qkv, wq, wk, eps, M, D, rstd_q, rstd_k, m_dev);
-  return ivh_host::check_launch("qk_rmsnorm_fwd");
+  return launch_row_width("qk_rmsnorm_fwd", nch_for(D), 8, TOO_WIDE, [&](auto N, auto W) {
+    hipLaunchKernelGGL((qk_rmsnorm_fwd_kernel<N(), W()>), dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream, qkv, wq, wk, eps, M, D, rstd_q, rstd_k, m_dev);
+  });
 }
 extern "C" int ivh_qk_rmsnorm_fwd(uint16_t* qkv, const float* wq, const float* wk, float eps, int M, int D,
                                   float* rstd_q, float* rstd_k, void* stream) {
@@ -1577,14 +1599,13 @@ static int qk_bwd_uses_b16(int M, int D) { return qk_bwd_b16() > 0 && (D / 8 + 2
 extern "C" int ivh_qk_norm_bwd_parts(int M, int D) {
   static const int cap = [] { const char* e = getenv("IVH_QKBWD_PARTS"); const int n = e ? atoi(e) : 0; return n >= 64 && n <= 8192 ? n : 768; }();
   if (qk_bwd_uses_b16(M, D) && (D / 8 + 255) / 256 == 1) return M < cap ? (M < 1 ? 1 : M) : cap;
-  return row_grid(M, BWD_PARTS_CAP);
+  return row_grid(M, bwd_parts_cap());
 }
 
 extern "C" int ivh_qk_rmsnorm_bwd_dyn(const uint16_t* qkv, uint16_t* dqkv, const float* wq, const float* wk,
                                       const float* rstd_q, const float* rstd_k, int M, int D,
                                       float* dwq_part, float* dwk_part, const int32_t* m_dev, void* stream) {
   IVH_REQUIRE(qkv && dqkv && wq && wk && rstd_q && rstd_k && dwq_part && dwk_part && M > 0 && D % 8 == 0, "qk_rmsnorm_bwd: bad args");
-  const int nch = nch_for(D);
   const int grid = ivh_qk_norm_bwd_parts(M, D);
   const int n4 = (D / 8 + 255) / 256;                        // 16-byte chunks per lane and segment when four waves share a token
   if (qk_bwd_uses_b16(M, D)) {
@@ -1592,9 +1613,10 @@ extern "C" int ivh_qk_rmsnorm_bwd_dyn(const uint16_t* qkv, uint16_t* dqkv, const
     else hipLaunchKernelGGL((qk_rmsnorm_bwd_b16_kernel<2>), dim3(grid), dim3(256), 0, (hipStream_t)stream, qkv, dqkv, wq, wk, rstd_q, rstd_k, M, D, dwq_part, dwk_part, m_dev);
     return ivh_host::check_launch("qk_rmsnorm_bwd");
   }
-  IVH_DISPATCH_NCH(nch, qk_rmsnorm_bwd_kernel, dim3(grid), dim3(256), (size_t)4 * D * sizeof(float), (hipStream_t)stream,
-                   qkv, dqkv, wq, wk, rstd_q, rstd_k, M, D, dwq_part, dwk_part, m_dev);
-  return ivh_host::check_launch("qk_rmsnorm_bwd");
+  return launch_row_width("qk_rmsnorm_bwd", nch_for(D), 8, TOO_WIDE, [&](auto N, auto W) {
+    hipLaunchKernelGGL((qk_rmsnorm_bwd_kernel<N(), W()>), dim3(grid), dim3(256), (size_t)4 * D * sizeof(float), (hipStream_t)stream,
+                       qkv, dqkv, wq, wk, rstd_q, rstd_k, M, D, dwq_part, dwk_part, m_dev);
+  });
 }
 extern "C" int ivh_qk_rmsnorm_bwd(const uint16_t* qkv, uint16_t* dqkv, const float* wq, const float* wk,
                                   const float* rstd_q, const float* rstd_k, int M, int D,
@@ -1611,36 +1633,36 @@ extern "C" int ivh_ln_l2_fwd(const uint16_t* y, const float* w, const float* b, 
   // nothing per column: 192-203 us per 53376 x 3200 launch = 3.4 TB/s.  A wave holding the whole row (5-8 chunks per lane, 56 + 28 registers at
   // 3200) reduces with shuffles only.  IVH_LNL2_FWD_WIDE=4 restores the shared-row form (A/B).
   static const int wide = [] { const char* e = getenv("IVH_LNL2_FWD_WIDE"); return e ? atoi(e) : 1; }();
+  const auto launch = [&](auto N, auto W) {
+    hipLaunchKernelGGL((ln_l2_fwd_kernel<N(), W()>), dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
+                       y, w, b, eps, M, C, out, stats, target, target_bf16, loss_rows);
+  };
   if (nch >= 5 && nch <= 8 && wide == 1) {
-    const dim3 grid(row_grid(M, 8192)), block(256);
-#define IVH_LNL2_FWD1(N) hipLaunchKernelGGL((ln_l2_fwd_kernel<N, 1>), grid, block, 0, (hipStream_t)stream, y, w, b, eps, M, C, out, stats, target, target_bf16, loss_rows)
-    if (nch == 5) IVH_LNL2_FWD1(5); else if (nch == 6) IVH_LNL2_FWD1(6); else if (nch == 7) IVH_LNL2_FWD1(7); else IVH_LNL2_FWD1(8);
-#undef IVH_LNL2_FWD1
-    return ivh_host::check_launch("ln_l2_fwd");
+    const int_c<1> one;
+    if (nch == 5) launch(int_c<5>{}, one); else if (nch == 6) launch(int_c<6>{}, one); else if (nch == 7) launch(int_c<7>{}, one); else launch(int_c<8>{}, one);
+    return check_launch("ln_l2_fwd");
   }
-  IVH_DISPATCH_NCH(nch, ln_l2_fwd_kernel, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                   y, w, b, eps, M, C, out, stats, target, target_bf16, loss_rows);
-  return ivh_host::check_launch("ln_l2_fwd");
+  return launch_row_width("ln_l2_fwd", nch, 8, TOO_WIDE, launch);
 }
 
 extern "C" int ivh_ln_l2_bwd(const uint16_t* y, const float* w, const float* b, const float* stats, const void* dout, int dout_bf16,
                              const void* target, int target_bf16, float dscale, const float* dscale_dev, int M, int C,
                              uint16_t* dy, float* dw_part, float* db_part, void* stream) {
   IVH_REQUIRE(y && w && b && stats && dy && dw_part && db_part && (dout || target) && M > 0 && C % 8 == 0, "ln_l2_bwd: bad args");
-  const int nch = nch_for(C);
-  const int grid = row_grid(M, BWD_PARTS_CAP);
+  const int grid = row_grid(M, bwd_parts_cap());
   static const int pf = [] { const char* e = getenv("IVH_LNL2_PF"); return e ? atoi(e) : 1; }();      // IVH_LNL2_PF=0: the generic kernel (A/B)
   const int n4 = (C / 8 + 255) / 256;
   if (pf > 0 && !dout && target && target_bf16 && n4 <= 2 && (long)M * C * 2 < (1L << 31)) {
-#define IVH_LNL2_PF_LAUNCH(N) hipLaunchKernelGGL((ln_l2_bwd_pf_kernel<N>), dim3(grid), dim3(256), 0, (hipStream_t)stream, y, w, b, stats, \
-    (const bf16_t*)target, dscale, dscale_dev, M, C, dy, dw_part, db_part)
-    if (n4 == 1) IVH_LNL2_PF_LAUNCH(1); else IVH_LNL2_PF_LAUNCH(2);
-#undef IVH_LNL2_PF_LAUNCH
-    return ivh_host::check_launch("ln_l2_bwd");
+    for_bool(n4 == 2, [&](auto WIDE) {
+      hipLaunchKernelGGL((ln_l2_bwd_pf_kernel<decltype(WIDE)::value ? 2 : 1>), dim3(grid), dim3(256), 0, (hipStream_t)stream, y, w, b, stats,
+                         (const bf16_t*)target, dscale, dscale_dev, M, C, dy, dw_part, db_part);
+    });
+    return check_launch("ln_l2_bwd");
   }
-  IVH_DISPATCH_NCH(nch, ln_l2_bwd_kernel, dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream,
-                   y, w, b, stats, dout, dout_bf16, target, target_bf16, dscale, dscale_dev, M, C, dy, dw_part, db_part);
-  return ivh_host::check_launch("ln_l2_bwd");
+  return launch_row_width("ln_l2_bwd", nch_for(C), 8, TOO_WIDE, [&](auto N, auto W) {
+    hipLaunchKernelGGL((ln_l2_bwd_kernel<N(), W()>), dim3(grid), dim3(256), (size_t)4 * C * sizeof(float), (hipStream_t)stream,
+                       y, w, b, stats, dout, dout_bf16, target, target_bf16, dscale, dscale_dev, M, C, dy, dw_part, db_part);
+  });
 }
 
 extern "C" int ivh_sum_rows(const float* x, int n, float scale, float* out, void* stream) {
@@ -1649,29 +1671,17 @@ extern "C" int ivh_sum_rows(const float* x, int n, float scale, float* out, void
   return ivh_host::check_launch("sum_rows");
 }
 
-#define IVH_DISPATCH_NCH_T(nch, KERNEL, TX, grid, block, shmem, s, ...)                                  \
-  switch (nch) {                                                                                         \
-    case 1: hipLaunchKernelGGL((KERNEL<1, TX>), grid, block, shmem, s, __VA_ARGS__); break;              \
-    case 2: hipLaunchKernelGGL((KERNEL<2, TX>), grid, block, shmem, s, __VA_ARGS__); break;              \
-    case 3: hipLaunchKernelGGL((KERNEL<3, TX>), grid, block, shmem, s, __VA_ARGS__); break;              \
-    case 4: hipLaunchKernelGGL((KERNEL<4, TX>), grid, block, shmem, s, __VA_ARGS__); break;              \
-    case 5: case 6: case 7: case 8: hipLaunchKernelGGL((KERNEL<2, TX, 4>), grid, block, shmem, s, __VA_ARGS__); break; \
-    default: ivh_host::set_error("row width %d not supported (max 4096)", (nch) * 512); return -1;       \
-  }
-
 extern "C" int ivh_layernorm_fwd(const void* x, int x_fp32, const float* w, const float* b, const float* w2, const float* b2,
                                  float eps, int M, int C, uint16_t* y, uint16_t* y2, float* stats, void* stream) {
   IVH_REQUIRE(x && w && b && y && stats && M > 0 && C % 8 == 0, "layernorm_fwd: bad args");
   IVH_REQUIRE((y2 == nullptr) == (w2 == nullptr) && (w2 == nullptr) == (b2 == nullptr), "layernorm_fwd: second head needs w2, b2, y2");
-  const int nch = nch_for(C);
-  if (x_fp32) {
-    IVH_DISPATCH_NCH_T(nch, layernorm_fwd_kernel, float, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                       (const float*)x, w, b, w2, b2, eps, M, C, y, y2, stats);
-  } else {
-    IVH_DISPATCH_NCH_T(nch, layernorm_fwd_kernel, bf16_t, dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)x, w, b, w2, b2, eps, M, C, y, y2, stats);
-  }
-  return ivh_host::check_launch("layernorm_fwd");
+  return launch_row_width("layernorm_fwd", nch_for(C), 8, TOO_WIDE, [&](auto N, auto W) {
+    for_bool(x_fp32, [&](auto FP32) {
+      using TX = std::conditional_t<decltype(FP32)::value, float, bf16_t>;
+      hipLaunchKernelGGL((layernorm_fwd_kernel<decltype(N)::value, TX, decltype(W)::value>), dim3(row_grid(M, 8192)), dim3(256), 0, (hipStream_t)stream,
+                         (const TX*)x, w, b, w2, b2, eps, M, C, y, y2, stats);
+    });
+  });
 }
 
 extern "C" int ivh_layernorm_bwd(const void* x, int x_fp32, const float* w, const float* w2, const float* stats,
@@ -1679,17 +1689,15 @@ extern "C" int ivh_layernorm_bwd(const void* x, int x_fp32, const float* w, cons
                                  float* dw_part, float* db_part, float* dw2_part, float* db2_part, void* stream) {
   IVH_REQUIRE(x && w && stats && dy && dx && dw_part && db_part && M > 0 && C % 8 == 0, "layernorm_bwd: bad args");
   IVH_REQUIRE((dy2 == nullptr) == (w2 == nullptr), "layernorm_bwd: second head needs w2 and dy2");
-  const int nch = nch_for(C);
-  const int grid = row_grid(M, BWD_PARTS_CAP);
+  const int grid = row_grid(M, bwd_parts_cap());
   const size_t sh = (size_t)4 * C * sizeof(float);
-  if (x_fp32) {
-    IVH_DISPATCH_NCH_T(nch, layernorm_bwd_kernel, float, dim3(grid), dim3(256), sh, (hipStream_t)stream,
-                       (const float*)x, w, w2, stats, dy, dy2, M, C, dx, accumulate, dw_part, db_part, dw2_part, db2_part);
-  } else {
-    IVH_DISPATCH_NCH_T(nch, layernorm_bwd_kernel, bf16_t, dim3(grid), dim3(256), sh, (hipStream_t)stream,
-                       (const bf16_t*)x, w, w2, stats, dy, dy2, M, C, dx, accumulate, dw_part, db_part, dw2_part, db2_part);
-  }
-  return ivh_host::check_launch("layernorm_bwd");
+  return launch_row_width("layernorm_bwd", nch_for(C), 8, TOO_WIDE, [&](auto N, auto W) {
+    for_bool(x_fp32, [&](auto FP32) {
+      using TX = std::conditional_t<decltype(FP32)::value, float, bf16_t>;
+      hipLaunchKernelGGL((layernorm_bwd_kernel<decltype(N)::value, TX, decltype(W)::value>), dim3(grid), dim3(256), sh, (hipStream_t)stream,
+                         (const TX*)x, w, w2, stats, dy, dy2, M, C, dx, accumulate, dw_part, db_part, dw2_part, db2_part);
+    });
+  });
 }
 
 extern "C" int ivh_token_mean_fwd(const float* x, int B, int L, int D, float* out, void* stream) {

@@ -76,6 +76,7 @@ SIGNATURES = {
     "ivh_gemm256_half_plan": [C.POINTER(GemmDesc), _i32, C.POINTER(_i32)],
     "ivh_gemm256_debug_half": [_i32],
     "ivh_gemm256_debug_route": [C.POINTER(GemmDesc), _i32, _i32, C.POINTER(_i32)],
+    "ivh_rmsnorm_add_debug_route": [_i32, _i32, _u32, _i32, _i32, _i32, C.POINTER(_i32)],
     "ivh_gemm256_half_rounds": [C.POINTER(GemmDesc)],
     "ivh_attn32_debug_stamps": [_vp, _i64],
     "ivh_gemm_split_workspace": [C.POINTER(GemmDesc)],

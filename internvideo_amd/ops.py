@@ -359,6 +359,13 @@ def gemm_fp8(a: torch.Tensor, b: torch.Tensor, scale_a: torch.Tensor, scale_b: t
     return (out, pre) if want_preact else out
 
 
+def _chk_slots(what: str, ns: int, branch_slot: Optional[torch.Tensor], y_slot: Optional[torch.Tensor]) -> None:
+    """the keep maps of droppath_plan as the _skip entry points read them: one int32 per sample, in HBM"""
+    for t, n in ((branch_slot, "branch_slot"), (y_slot, "y_slot")):
+        if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.numel() != ns or not t.is_contiguous()):
+            raise InternVideoHipError(f"{what}: {n} must be a contiguous int32 [{ns}] tensor in HBM")
+
+
 def rmsnorm_add_fwd(res_in: Optional[torch.Tensor], branch: Optional[torch.Tensor], gamma: Optional[torch.Tensor],
                     rowscale: Optional[torch.Tensor], rows_per_sample: int, w: Optional[torch.Tensor], eps: float,
                     want_res_out: bool = True, res_dtype: Optional[torch.dtype] = None,
@@ -384,10 +391,7 @@ def rmsnorm_add_fwd(res_in: Optional[torch.Tensor], branch: Optional[torch.Tenso
     rb = 4 if rt == F32 else 2
     nbytes = M * D * ((rb if res_in is not None else 0) + (2 if branch is not None else 0) + (rb if want_res_out else 0) + (2 if w is not None else 0))
     if branch_slot is not None or y_slot is not None:
-        ns = M // int(rows_per_sample)
-        for t, n in ((branch_slot, "branch_slot"), (y_slot, "y_slot")):
-            if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.numel() != ns or not t.is_contiguous()):
-                raise InternVideoHipError(f"rmsnorm_add_fwd: {n} must be a contiguous int32 [{ns}] tensor in HBM")
+        _chk_slots("rmsnorm_add_fwd", M // int(rows_per_sample), branch_slot, y_slot)
         _pcall("rmsnorm_add_fwd", nbytes, "B", "ivh_rmsnorm_add_fwd_skip", ptr(res_in), int(rt == BF16), ptr(branch), ptr(gamma), ptr(rowscale),
                int(rows_per_sample), ptr(w), float(eps), M, D, ptr(res_out), ptr(y), ptr(rstd), ptr(branch_slot), ptr(y_slot), stream_ptr())
         return res_out, y, rstd
@@ -498,10 +502,7 @@ def rmsnorm_add_bwd(dy: Optional[torch.Tensor], dres_out: Optional[torch.Tensor]
                       (2 if (branch is not None and dg_part is not None) else 0) + rb + (2 if want_dbranch else 0) + (2 if dres_extra is not None else 0))
     extra = () if rt == F32 else (ptr(dres_extra),)
     if y_slot is not None or branch_slot is not None:       # dy / branch / dbranch compacted over the kept samples of their DropPath draws
-        ns = M // int(rows_per_sample)
-        for t, n in ((branch_slot, "branch_slot"), (y_slot, "y_slot")):
-            if t is not None and (not t.is_cuda or t.dtype != torch.int32 or t.numel() != ns or not t.is_contiguous()):
-                raise InternVideoHipError(f"rmsnorm_add_bwd: {n} must be a contiguous int32 [{ns}] tensor in HBM")
+        _chk_slots("rmsnorm_add_bwd", M // int(rows_per_sample), branch_slot, y_slot)
         _pcall("rmsnorm_add_bwd", nbytes, "B", "ivh_rmsnorm_add_bwd_skip", ptr(dy), ptr(dres_out), int(rt == BF16), ptr(res_out), ptr(rstd), ptr(w), ptr(branch),
                ptr(gamma), ptr(rowscale), int(rows_per_sample), M, D, ptr(dres_in), ptr(dbranch), ptr(dw_part), ptr(dg_part), ptr(db_part), ptr(dres_extra),
                ptr(y_slot), ptr(branch_slot), stream_ptr())
