@@ -26,7 +26,8 @@ int ivh_version(void);
  *       ivh_qk_norm_bwd_parts(M, D) (up to 768 rows) instead of ivh_norm_bwd_parts(M) (up to 512).
  *   2 = round 6: ivh_gemm_desc grew by two trailing pointers (m_dev, k_dev: a descriptor allocated with the old size must not be passed);
  *       new entry points ivh_droppath_plan, ivh_rmsnorm_add_{fwd,bwd}_skip, ivh_colsum_finish_dyn, ivh_qk_rmsnorm_{fwd,bwd}_dyn,
- *       ivh_flash_attn_{fwd,bwd}_dyn.  Every signature of ABI 1 (as of round 5) is unchanged. */
+ *       ivh_flash_attn_{fwd,bwd}_dyn.  Every signature of ABI 1 (as of round 5) is unchanged.
+ *       Added since, without a version step (additions only): ivh_mix_clips, ivh_soft_ce_rows, ivh_mixup_target. */
 #define IVH_ABI_VERSION 2
 int ivh_abi_version(void);
 /* Device-side dropout epoch.  The dropout masks of ivh_bert_embed_*, ivh_add_layernorm_* and ivh_flash_attn_*_dropout are counter based:
@@ -512,6 +513,40 @@ int ivh_add_layernorm_bwd(const uint16_t* a, const uint16_t* r, int act, const f
  * the loss) or NULL = 1.  dlogits may alias bf16 logits (ldd == ld): each element is read before it is overwritten. */
 int ivh_ce_rows(const void* logits, int logits_fp32, int ld, int M, int V, const int* labels, int ignore_index, float dscale,
                 const float* dscale_dev, float* inv_count, float* rows, uint16_t* dlogits, int ldd, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Fine-tuning step (single_modality/run_finetuning.py:116-148 defaults --mixup 0.8 --cutmix 1.0 --smoothing 0.1; csrc/finetune.hip).
+ *
+ * ivh_mix_clips: Mixup / CutMix of a clip batch fused with the cast (datasets/mixup.py:159-207 `_mix_elem` / `_mix_batch` on the fp32 clips,
+ * then `.bfloat16()`, engines/engine_for_finetuning.py:63-67).  x fp32|bf16 [B][C][T][H][W] contiguous, out bf16|fp32 of the same shape, a
+ * DIFFERENT buffer (sample i reads sample B-1-i); C*T*H*W % 4 == 0; both 16-byte aligned.  Read from device memory: table int32 [B][8] =
+ * {src, kind, yl, yh, xl, xh, bits(lam), bits(oml)} per sample (lam / oml: the fp32 bit patterns).
+ *   kind 0: out = x[i];   kind 1: out = rn(rn(x[i] * lam) + rn(x[src] * oml)) -- two rounded fp32 products and a rounded sum, no FMA, which
+ *   is what the reference's separate torch ops compute;   kind 2: out = x[src] where yl <= y < yh and xl <= x < xh (every c, t), else x[i]:
+ *   a select, nothing of the other operand reaches the output.  A bf16 output is the round-to-nearest-even of that fp32 value.
+ *   A sample whose kind is not 0..2 or whose src is outside [0, B) passes through unmixed (the table is not visible to the host). */
+int ivh_mix_clips(const void* x, int x_fp32, const int32_t* table, int B, int C, int T, int H, int W, void* out, int out_fp32, void* stream);
+/* ivh_soft_ce_rows: timm's SoftTargetCrossEntropy `torch.sum(-target * F.log_softmax(x, dim=-1), dim=-1).mean()` (run_finetuning.py:593-597)
+ * over logits bf16|fp32 [M][ld] with V live columns (ld % 8 == 0; columns V..ld-1 are padding: out of the softmax, out of V in the
+ * smoothing, zero gradient -- the convention of ivh_ce_rows), forward, gradient and rank in one launch.  The target, one of
+ *   factored: label_a, label_b int32 [M] (label_b NULL = label_a), mix fp32 [M][2] = (lam, oml) per row (NULL = (1, 0)), all read from
+ *             device memory, and the host scalar `smoothing`: with off = smoothing / V, on = 1 - smoothing + off (computed in double,
+ *             rounded to fp32) t_c = rn(rn((c == a ? on : off) * lam) + rn((c == b ? on : off) * oml)), `mixup_target` of
+ *             datasets/mixup.py:22-27.  lam = 1: timm LabelSmoothingCrossEntropy; smoothing = 0 without mix: the plain mean CE;
+ *   dense:    target fp32 [M][ldt] (ldt >= V), label_b = mix = NULL; what the reference's Mixup.__call__ returns.
+ * rows[m] = (1 / M) * sum_c t_c (logsumexp - x_c) in fp32, max-subtracted; loss (device scalar, or NULL) = their sum through ivh_sum_rows.
+ * dlogits bf16 [M][ldd] (or NULL; ldd % 8 == 0, ldd >= V; never the logits' buffer) = dscale * dscale_dev[0] / M * (T softmax(x) - t) with
+ * T = sum_c t_c taken from the target as given (nothing assumes it is 1), zeros in columns >= V.  dscale_dev: device scalar (the upstream
+ * gradient, e.g. 1 / update_freq) or NULL = 1.  rank int32 [M] (or NULL; needs label_a, also next to a dense target) = #{c : x_c > x_a} +
+ * #{c < a : x_c == x_a}, the position of label_a in the row's descending order: top-k accuracy is rank < k (utils.accuracy of
+ * engine_for_finetuning.py:173,225). */
+int ivh_soft_ce_rows(const void* logits, int logits_fp32, int ld, int M, int V, const int32_t* label_a, const int32_t* label_b,
+                     const float* mix, double smoothing, const float* target, int64_t ldt, float dscale, const float* dscale_dev,
+                     float* rows, float* loss, uint16_t* dlogits, int ldd, int32_t* rank, void* stream);
+/* ivh_mixup_target: the dense target of datasets/mixup.py:22-27 for callers that keep the reference's loop: out fp32 [M][V],
+ * out[i][c] = rn(rn(v1 * lam_i) + rn(v2 * oml_i)), v1 = (c == labels[i] ? on : off), v2 = (c == labels[M-1-i] ? on : off) (`target.flip(0)`),
+ * on / off as above.  Read from device memory: labels int32 [M], mix fp32 [M][2]. */
+int ivh_mixup_target(const int32_t* labels, const float* mix, int M, int V, double smoothing, float* out, void* stream);
 
 #ifdef __cplusplus
 }

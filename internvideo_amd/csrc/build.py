@@ -9,11 +9,14 @@ from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
-SOURCES = ["host.hip", "gemm.hip", "gemm256.hip", "gemm_fp8.hip", "norms.hip", "flash_attn.hip", "flash_attn32.hip", "embed.hip", "optim.hip", "contrastive.hip", "teacher.hip", "videomae.hip", "bert.hip"]
+SOURCES = ["host.hip", "gemm.hip", "gemm256.hip", "gemm_fp8.hip", "norms.hip", "flash_attn.hip", "flash_attn32.hip", "embed.hip", "optim.hip", "contrastive.hip", "teacher.hip", "videomae.hip", "bert.hip", "finetune.hip"]
 LIB = os.path.join(HERE, "libinternvideo_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result",
          "-ffp-contract=fast"]
+# Per-file additions.  -ffp-contract=fast DISREGARDS `#pragma clang fp contract(off)`; finetune.hip pins results bit for bit to separately
+# rounded products and sums, so it is built with the variant that honours the pragma (everything outside such a block still contracts).
+FILE_FLAGS = {"finetune.hip": ["-ffp-contract=fast-honor-pragmas"]}
 
 
 def _digest(paths):
@@ -22,6 +25,7 @@ def _digest(paths):
         with open(p, "rb") as f:
             h.update(f.read())
     h.update(" ".join(FLAGS).encode())
+    h.update(repr(sorted(FILE_FLAGS.items())).encode())
     return h.hexdigest()
 
 
@@ -46,7 +50,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
 
     def cc(src):
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
-        cmd = [HIPCC] + FLAGS + ["-c", src, "-o", obj]
+        cmd = [HIPCC] + FLAGS + FILE_FLAGS.get(os.path.basename(src), []) + ["-c", src, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError(f"hipcc failed for {src}:\n{r.stdout}\n{r.stderr}")

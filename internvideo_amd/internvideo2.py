@@ -20,6 +20,39 @@ from . import functional as Fn
 from .internvideo2_pretrain import AttentionPoolingBlock, Block, PatchEmbed, PretrainInternVideo2, RMSNorm, _trunc_normal_, register_model
 
 
+class PaddedHeadFn(torch.autograd.Function):
+    """y = x W^T + b for a head whose width n is not a multiple of 8: the GEMM runs on W / b zero-padded to the next multiple (as
+    xbert.LinearCrossEntropyFn does) and the result is the `[:, :n]` view of the padded logits, whose row pitch the loss kernels accept as
+    it is.  The padding happens INSIDE the function, so the gradients are delivered to the head's own parameters (`_ret_grad`: into the
+    training engine's buffers, overwriting like every other matrix gradient) instead of arriving through autograd's pad backward."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        x2 = x.reshape(-1, x.shape[-1])
+        x2 = (x2 if x2.dtype == torch.bfloat16 else x2.to(torch.bfloat16)).contiguous()
+        n = w.shape[0]
+        pad = 8 - n % 8
+        W, bias = F.pad(Fn.mat(w), (0, 0, 0, pad)), F.pad(Fn.vec(b), (0, pad))
+        y = Fn.ops.gemm(x2, W, bias=bias)
+        ctx.save_for_backward(x2, W)
+        ctx.p, ctx.n, ctx.xshape, ctx.xdtype = (w, b), n, x.shape, x.dtype
+        return y.reshape(*x.shape[:-1], n + pad)[..., :n]
+
+    @staticmethod
+    def backward(ctx, dy):
+        x2, W = ctx.saved_tensors
+        w, b = ctx.p
+        n = ctx.n
+        dl = x2.new_zeros((x2.shape[0], W.shape[0]))
+        dl[:, :n].copy_(dy.reshape(-1, n))
+        dx = Fn.ops.gemm(dl, W, a_kc=True, b_kc=False).reshape(ctx.xshape).to(ctx.xdtype) if ctx.needs_input_grad[0] else None
+        M = dl.shape[0]
+        dlp, xp = (dl, x2) if M % 8 == 0 else (F.pad(dl, (0, 0, 0, 8 - M % 8)), F.pad(x2, (0, 0, 0, 8 - M % 8)))   # the transposing GEMM reads 8-row groups
+        dW = Fn._ret_grad(w, Fn.ops.gemm(dlp, xp, a_kc=False, b_kc=False)[:n])
+        db = Fn._ret_grad(b, Fn.ops.colsum_bf16(dl)[:n])
+        return dx, dW, db
+
+
 class InternVideo2(PretrainInternVideo2):
     """F:337-543.  Inherits the token / block machinery of the pre-training student (forward_features with mask=None)."""
 
@@ -97,12 +130,16 @@ class InternVideo2(PretrainInternVideo2):
         w, b = self.head.weight, self.head.bias
         n = w.shape[0]
         if n % 8:                                          # class counts like 174 / 339: the GEMM moves 8-column chunks -> zero-pad
-            pad = 8 - n % 8
-            w, b = F.pad(w, (0, 0, 0, pad)), F.pad(b, (0, pad))
+            return PaddedHeadFn.apply(h, w, b)
         return Fn.LinearFn.apply(h, w, b)[:, :n]
 
-    def forward_loss(self, *a, **k):
-        raise NotImplementedError("fine-tuning losses (cross-entropy / mixup) are the caller's (engines/engine_for_finetuning.py)")
+    def forward_loss(self, x, target, target_b=None, mix=None, smoothing: float = 0.0):
+        """the fine-tuning step's loss (engines/engine_for_finetuning.py:13-17 with the criterion of run_finetuning.py:593-599) in one
+        row kernel: x (B, C, T, H, W), target / target_b integer labels (B,), mix fp32 (B, 2) = (lam, oml) per row -- what
+        finetune.Mixup.apply returns; target alone: (label-smoothed) cross entropy -> (loss, logits.detach())"""
+        from .finetune import soft_cross_entropy
+        logits = self.forward(x)
+        return soft_cross_entropy(logits, target, target_b, mix, smoothing), logits.detach()
 
 
 def _ft(embed_dim, depth, num_heads, mlp_ratio, **kwargs):

@@ -1133,6 +1133,91 @@ def ce_rows(logits: torch.Tensor, labels: torch.Tensor, V: Optional[int] = None,
     return sum_rows(rows, 1.0), dl
 
 
+# ---- fine-tuning step (finetune.hip) --------------------------------------------------------------------------------------
+def mix_clips(x: torch.Tensor, table: torch.Tensor, out_dtype=BF16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Mixup / CutMix of a clip batch fused with the cast.  x fp32|bf16 (B, C, T, H, W) contiguous; table int32 (B, 8) in HBM =
+    (src, kind, yl, yh, xl, xh, bits(lam), bits(oml)) per sample (finetune.Mixup.draw builds it) -> a NEW tensor of out_dtype (bf16|fp32)."""
+    _L.require_gpu()
+    if not x.is_cuda or not table.is_cuda:
+        raise InternVideoHipError("mix_clips: x and table must live in HBM; there is no CPU path")
+    if x.dtype not in (BF16, F32) or out_dtype not in (BF16, F32) or x.dim() != 5 or not x.is_contiguous():
+        raise InternVideoHipError("mix_clips: x must be a contiguous bf16 / fp32 (B, C, T, H, W) batch, out_dtype bf16 / fp32")
+    B, Cc, T, H, W = x.shape
+    _chk_rows(table, torch.int32, "table")
+    if tuple(table.shape) != (B, 8):
+        raise InternVideoHipError(f"mix_clips: table must be int32 ({B}, 8), got {tuple(table.shape)}")
+    if out is None:
+        out = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+    elif out.dtype != out_dtype or out.shape != x.shape or not out.is_contiguous() or not out.is_cuda or out.data_ptr() == x.data_ptr():
+        raise InternVideoHipError("mix_clips: out must be another contiguous HBM tensor of x's shape and of out_dtype")
+    kinds_bytes = x.numel() * (2 * x.element_size() + out.element_size())       # upper bound: both operands read (kind 1)
+    _pcall("mix_clips", kinds_bytes, "B", "ivh_mix_clips", ptr(x), int(x.dtype == F32), ptr(table), B, Cc, T, H, W, ptr(out), int(out_dtype == F32),
+           stream_ptr())
+    return out
+
+
+def soft_ce_rows(logits: torch.Tensor, label_a: Optional[torch.Tensor], label_b: Optional[torch.Tensor] = None,
+                 mix: Optional[torch.Tensor] = None, smoothing: float = 0.0, V: Optional[int] = None, target: Optional[torch.Tensor] = None,
+                 dscale: float = 1.0, dscale_dev: Optional[torch.Tensor] = None, want_grad: bool = True, want_rank: bool = False):
+    """soft-target cross entropy, mean over the M rows.  logits bf16|fp32 [M, ld] (columns >= V are padding).  Target: factored
+    (label_a, label_b | None = label_a, mix fp32 [M, 2] = (lam, oml) | None = (1, 0), smoothing) or dense (target fp32 [M, >= V]).
+    -> (loss fp32 [1], dlogits bf16 [M, ld] | None = dscale * dscale_dev * d loss / d logits, rank int32 [M] | None = position of label_a)"""
+    _L.require_gpu()
+    if not logits.is_cuda:
+        raise InternVideoHipError(f"soft_ce_rows: logits must live in HBM (got device {logits.device}); there is no CPU path")
+    if logits.dtype not in (BF16, F32) or logits.dim() != 2 or logits.stride(1) != 1:
+        raise InternVideoHipError("soft_ce_rows: logits must be a bf16 / fp32 matrix with contiguous rows")
+    M, ld = logits.shape[0], logits.stride(0)
+    V = logits.shape[1] if V is None else int(V)
+    la = lb = None
+    if label_a is not None:
+        la = _ids32(label_a, "label_a")
+        if la.numel() != M:
+            raise InternVideoHipError("soft_ce_rows: one label per row")
+    if label_b is not None:
+        lb = _ids32(label_b, "label_b")
+        if lb.numel() != M:
+            raise InternVideoHipError("soft_ce_rows: one label_b per row")
+    ldt = 0
+    if target is not None:
+        _chk(target, F32, "target")
+        if target.dim() != 2 or target.shape[0] != M or target.shape[1] < V or label_b is not None or mix is not None:
+            raise InternVideoHipError("soft_ce_rows: a dense target is fp32 [M, >= V] and comes without label_b / mix")
+        ldt = target.stride(0)
+    elif la is None:
+        raise InternVideoHipError("soft_ce_rows: give label_a (factored target) or target (dense)")
+    if mix is not None:
+        _chk_rows(mix, F32, "mix")
+        if tuple(mix.shape) != (M, 2):
+            raise InternVideoHipError(f"soft_ce_rows: mix must be fp32 ({M}, 2)")
+    if want_rank and la is None:
+        raise InternVideoHipError("soft_ce_rows: rank is the position of label_a")
+    if dscale_dev is not None:
+        _chk(dscale_dev, F32, "dscale_dev", inner_contig=False)    # one scalar is read: an expanded (stride 0) upstream gradient is fine
+    dev = logits.device
+    rows = torch.empty((M,), dtype=F32, device=dev)
+    loss = torch.empty((1,), dtype=F32, device=dev)
+    dl = torch.empty((M, ld), dtype=BF16, device=dev) if want_grad else None
+    rank = torch.empty((M,), dtype=torch.int32, device=dev) if want_rank else None
+    nbytes = M * V * (logits.element_size() * 2 + (2 if want_grad else 0) + (8 if target is not None else 0))
+    _pcall("soft_ce_rows", nbytes, "B", "ivh_soft_ce_rows", ptr(logits), int(logits.dtype == F32), ld, M, V, ptr(la), ptr(lb), ptr(mix),
+           float(smoothing), ptr(target), ldt, float(dscale), ptr(dscale_dev), ptr(rows), ptr(loss), ptr(dl), ld, ptr(rank), stream_ptr())
+    return loss, dl, rank
+
+
+def mixup_target(labels: torch.Tensor, mix: torch.Tensor, smoothing: float, V: int) -> torch.Tensor:
+    """dense fp32 [M, V] target of datasets/mixup.py:22-27 from labels [M] (the partner of row i is row M-1-i) and mix fp32 [M, 2]"""
+    _L.require_gpu()
+    _chk_rows(mix, F32, "mix")
+    lab = _ids32(labels, "labels")
+    M = lab.numel()
+    if tuple(mix.shape) != (M, 2):
+        raise InternVideoHipError(f"mixup_target: mix must be fp32 ({M}, 2)")
+    out = torch.empty((M, int(V)), dtype=F32, device=mix.device)
+    _pcall("mixup_target", M * int(V) * 4, "B", "ivh_mixup_target", ptr(lab), ptr(mix), M, int(V), float(smoothing), ptr(out), stream_ptr())
+    return out
+
+
 # ---- optimizer --------------------------------------------------------------------------------------------------------
 def adamw_step(master, exp_avg, exp_avg_sq, grad, shadow, lr, beta1, beta2, eps, weight_decay, step,
                grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None, lr_segments=None, seg_base: int = 0) -> None:

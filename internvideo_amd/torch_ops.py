@@ -16,7 +16,7 @@ Two groups:
   * building blocks (gemm, gemm_dact, flash_attn_bwd, rmsnorm_add_fwd / _bwd, qk_rmsnorm_bwd, layernorm_fwd, add_layernorm_fwd,
     cross_entropy_rows, gemm_grouped, adamw_step_ ...): forward / backward kernels as plain operators, no autograd formula;
   * the DIFFERENTIABLE fused-op seam of SURVEY.md 8(b) B3 -- `linear`, `fused_mlp`, `rmsnorm_add`, `qk_rmsnorm`, `flash_attn_fwd`,
-    `patch_embed_gather`, `decoder_ln_l2_cos_loss`, `contrastive_logits_ce` -- each registered with `torch.library.register_autograd`
+    `patch_embed_gather`, `decoder_ln_l2_cos_loss`, `contrastive_logits_ce`, `soft_target_cross_entropy` -- each registered with `torch.library.register_autograd`
     (its backward is again a registered operator), checked by `torch.library.opcheck` in tests/test_torch_ops_gpu.py.  The drop-in modules
     of internvideo_amd.fused_ops (FlashAttention, FusedMLP, DropoutAddRMSNorm) dispatch through these.  The whole-model mirrors fuse
     further (the residual protocol, deferred / grouped weight gradients, engine-owned gradient buffers live in functional.BlockStackFn,
@@ -533,9 +533,68 @@ for _name, _bwd, _setup in (("qk_rmsnorm", _qkn_autograd, _qkn_setup), ("linear"
                             ("decoder_ln_l2_cos_loss", _lnl2_autograd, _lnl2_setup), ("contrastive_logits_ce", _vtc_autograd, _vtc_setup)):
     torch.library.register_autograd("internvideo_hip::" + _name, _bwd, setup_context=_setup, lib=_LIB)
 
+# ---- fine-tuning step: Mixup / CutMix of the clips, soft-target cross entropy (finetune.hip) ------------------------------------------------
+_LIB.define("mix_clips(Tensor x, Tensor table, bool out_fp32=False) -> Tensor")
+_LIB.define("soft_target_cross_entropy(Tensor logits, Tensor? label_a, Tensor? label_b=None, Tensor? mix=None, float smoothing=0.0, "
+            "Tensor? target=None) -> Tensor")
+_LIB.define("soft_target_cross_entropy_bwd(Tensor dloss, Tensor logits, Tensor? label_a, Tensor? label_b, Tensor? mix, float smoothing, "
+            "Tensor? target) -> Tensor")
+
+
+def _mixc(x, table, out_fp32=False):
+    return ops.mix_clips(x, table, F32 if out_fp32 else BF16)
+
+
+def _mixc_meta(x, table, out_fp32=False):
+    return x.new_empty(x.shape, dtype=F32 if out_fp32 else BF16)
+
+
+from .finetune import _kernel_rows as _rows8  # noqa: E402  (the pitch / padding rule the modules use)
+
+
+def _stce(logits, label_a, label_b=None, mix=None, smoothing=0.0, target=None):
+    lg, V = _rows8(logits)
+    return ops.soft_ce_rows(lg, label_a, label_b, _f32(mix), smoothing, V=V, target=_f32(target), want_grad=False)[0]
+
+
+def _stce_meta(logits, label_a, label_b=None, mix=None, smoothing=0.0, target=None):
+    return logits.new_empty((1,), dtype=F32)
+
+
+def _stce_bwd(dloss, logits, label_a, label_b, mix, smoothing, target):
+    lg, V = _rows8(logits)
+    dl = ops.soft_ce_rows(lg, label_a, label_b, _f32(mix), smoothing, V=V, target=_f32(target), want_grad=True,
+                          dscale_dev=dloss.reshape(1).float().contiguous())[1]
+    return dl[:, :V].contiguous()
+
+
+def _stce_bwd_meta(dloss, logits, label_a, label_b, mix, smoothing, target):
+    return logits.new_empty(logits.shape, dtype=BF16)
+
+
+def _stce_setup(ctx, inputs, output):
+    logits, label_a, label_b, mix, smoothing, target = inputs
+    ctx.save_for_backward(logits, label_a, label_b, mix, target)
+    ctx.smoothing = smoothing
+
+
+def _stce_autograd(ctx, dloss):
+    logits, label_a, label_b, mix, target = ctx.saved_tensors
+    dl = torch.ops.internvideo_hip.soft_target_cross_entropy_bwd(dloss, logits, label_a, label_b, mix, ctx.smoothing, target)
+    return dl.to(logits.dtype), None, None, None, None, None
+
+
+for _name, _impl, _meta in (("mix_clips", _mixc, _mixc_meta), ("soft_target_cross_entropy", _stce, _stce_meta),
+                            ("soft_target_cross_entropy_bwd", _stce_bwd, _stce_bwd_meta)):
+    _LIB.impl(_name, _impl, "CUDA")
+    _LIB.impl(_name, _meta, "Meta")
+torch.library.register_autograd("internvideo_hip::soft_target_cross_entropy", _stce_autograd, setup_context=_stce_setup, lib=_LIB)
+
+
 DIFFERENTIABLE: Tuple[str, ...] = ("linear", "fused_mlp", "rmsnorm_add", "qk_rmsnorm", "flash_attn_fwd", "patch_embed_gather",
-                                   "decoder_ln_l2_cos_loss", "contrastive_logits_ce")
+                                   "decoder_ln_l2_cos_loss", "contrastive_logits_ce", "soft_target_cross_entropy")
 OPERATORS: Tuple[str, ...] = ("gemm", "gemm_dact", "flash_attn_fwd", "flash_attn_bwd", "rmsnorm_add_fwd", "layernorm_fwd", "add_layernorm_fwd",
                               "cross_entropy_rows", "adamw_step_", "rmsnorm_add_bwd", "qk_rmsnorm", "qk_rmsnorm_bwd", "gemm_grouped", "linear",
                               "linear_bwd", "fused_mlp", "fused_mlp_bwd", "rmsnorm_add", "patch_embed_gather", "patch_embed_gather_bwd",
-                              "decoder_ln_l2_cos_loss", "decoder_ln_l2_cos_loss_bwd", "contrastive_logits_ce")
+                              "decoder_ln_l2_cos_loss", "decoder_ln_l2_cos_loss_bwd", "contrastive_logits_ce", "mix_clips",
+                              "soft_target_cross_entropy", "soft_target_cross_entropy_bwd")
