@@ -27,7 +27,8 @@ int ivh_version(void);
  *   2 = round 6: ivh_gemm_desc grew by two trailing pointers (m_dev, k_dev: a descriptor allocated with the old size must not be passed);
  *       new entry points ivh_droppath_plan, ivh_rmsnorm_add_{fwd,bwd}_skip, ivh_colsum_finish_dyn, ivh_qk_rmsnorm_{fwd,bwd}_dyn,
  *       ivh_flash_attn_{fwd,bwd}_dyn.  Every signature of ABI 1 (as of round 5) is unchanged.
- *       Added since, without a version step (additions only): ivh_mix_clips, ivh_soft_ce_rows, ivh_mixup_target. */
+ *       Added since, without a version step (additions only): ivh_mix_clips, ivh_soft_ce_rows, ivh_mixup_target; ivh_topk_rows_f32,
+ *       ivh_softmax_axis_f32, ivh_rerank_lists (+ ivh_rerank_lists_workspace_bytes), ivh_scatter_pair_scores, ivh_retrieval_ranks. */
 #define IVH_ABI_VERSION 2
 int ivh_abi_version(void);
 /* Device-side dropout epoch.  The dropout masks of ivh_bert_embed_*, ivh_add_layernorm_* and ivh_flash_attn_*_dropout are counter based:
@@ -547,6 +548,42 @@ int ivh_soft_ce_rows(const void* logits, int logits_fp32, int ld, int M, int V, 
  * out[i][c] = rn(rn(v1 * lam_i) + rn(v2 * oml_i)), v1 = (c == labels[i] ? on : off), v2 = (c == labels[M-1-i] ? on : off) (`target.flip(0)`),
  * on / off as above.  Read from device memory: labels int32 [M], mix fp32 [M][2]. */
 int ivh_mixup_target(const int32_t* labels, const float* mix, int M, int V, double smoothing, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stage-2 zero-shot retrieval evaluation (multi_modality/tasks/retrieval_utils.py: `evaluation` :226-613, `itm_eval` :1243-1303): the
+ * device work between feature extraction and the metrics.  Matrices are fp32 with a row and a column stride IN ELEMENTS, so the
+ * transposed direction (`t2i_scores`, `.T`) reads the same buffer.  Arguments are checked on the host (< 0, nothing launched), the work
+ * goes on `stream`, nothing synchronises.  Index values read from device memory that fall outside their matrix are skipped. */
+/* `sims.topk(k)` (:398, :503) for every row: out_val fp32 [n_rows][k], out_idx int32 [n_rows][k], the k largest entries in descending
+ * order, equal values by ascending column.  1 <= k <= min(n_cols, 1024).  The order is total on non-NaN floats (-0.0 == +0.0, -inf
+ * allowed); out_val holds the input's own bits.  NaN input: unspecified values, no out-of-bounds access. */
+int ivh_topk_rows_f32(const float* in, int n_rows, int n_cols, int64_t row_stride, int64_t col_stride, int k, float* out_val,
+                      int32_t* out_idx, void* stream);
+/* out[r][c] = softmax_c(in[r][:])[c], times in[r][c] when mul_input != 0: `s.softmax(dim=1)` / `s.T.softmax(dim=1)` (:598-612) and, read
+ * through transposed strides, the dual-softmax matrices `s * s.softmax(dim=0)` / `s.T * s.T.softmax(dim=0)` (:585-589).  `out` must be a
+ * dense row- or column-major matrix (one stride 1, the other >= the extent it steps over) that does not overlap `in`. */
+int ivh_softmax_axis_f32(const float* in, int n_rows, int n_cols, int64_t in_row_stride, int64_t in_col_stride, float* out,
+                         int64_t out_row_stride, int64_t out_col_stride, int mul_input, void* stream);
+/* The pairs the re-ranking loops of :396-483 (video -> its top-kv texts) and :501-566 (text -> its top-kt videos) score, grouped by video
+ * and each pair once: idx_v2t int32 [nv][kv], idx_t2v int32 [nt][kt] (ivh_topk_rows_f32 of the two directions); for the videos
+ * [v_begin, v_end) -> CSR: ptr int32 [v_end - v_begin + 1], cand int32 (text indices of each video, ascending, no duplicates), flags uint8
+ * (bit 0: the video chose the text, bit 1: the text chose the video).  cand and flags hold (v_end - v_begin) * kv + nt * kt slots (must fit
+ * int32); workspace: ivh_rerank_lists_workspace_bytes(v_end - v_begin, nt) bytes, 4-byte aligned. */
+int64_t ivh_rerank_lists_workspace_bytes(int n_videos, int nt);
+int ivh_rerank_lists(const int32_t* idx_v2t, int nv, int kv, const int32_t* idx_t2v, int nt, int kt, int v_begin, int v_end,
+                     int32_t* ptr, int32_t* cand, uint8_t* flags, void* workspace, void* stream);
+/* `i2t_scores_x[i, topk_idx] = score` (:483) and `t2i_scores_x[j, topk_idx] = score` (:566) from one score per cand entry (`capacity`
+ * slots in cand / flags / scores): scores[e] goes to x_v2t[i][j] where bit 0 of flags[e] is set and to x_t2v[j][i] where bit 1 is set,
+ * i = v_begin + the entry's row, j = cand[e].  No other element of x_v2t (nv x nt) / x_t2v (nt x nv) is written; both must be dense
+ * row- or column-major. */
+int ivh_scatter_pair_scores(const int32_t* ptr, const int32_t* cand, const uint8_t* flags, const float* scores, int64_t capacity,
+                            int v_begin, int n_videos, int nv, int nt, float* x_v2t, int64_t v2t_row_stride, int64_t v2t_col_stride,
+                            float* x_t2v, int64_t t2v_row_stride, int64_t t2v_col_stride, void* stream);
+/* `np.where(np.argsort(score)[::-1] == gt)` minimised over a row's ground truths (:1245-1280): rank int32 [n_rows],
+ * rank[r] = min over g in gt_idx[gt_ptr[r] .. gt_ptr[r+1]) of #{c : x[r][c] > x[r][g]} + #{c < g : x[r][c] == x[r][g]}; n_cols for a row
+ * without a ground truth inside the matrix.  Equal to the reference on rows without ties.  gt_ptr int32 [n_rows + 1], non-decreasing. */
+int ivh_retrieval_ranks(const float* scores, int n_rows, int n_cols, int64_t row_stride, int64_t col_stride, const int32_t* gt_ptr,
+                        const int32_t* gt_idx, int32_t* rank, void* stream);
 
 #ifdef __cplusplus
 }

@@ -151,6 +151,12 @@ SIGNATURES = {
     "ivh_mix_clips": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "ivh_soft_ce_rows": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, C.c_double, _vp, _i64, _f32, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "ivh_mixup_target": [_vp, _vp, _i32, _i32, C.c_double, _vp, _vp],
+    "ivh_topk_rows_f32": [_vp, _i32, _i32, _i64, _i64, _i32, _vp, _vp, _vp],
+    "ivh_softmax_axis_f32": [_vp, _i32, _i32, _i64, _i64, _vp, _i64, _i64, _i32, _vp],
+    "ivh_rerank_lists_workspace_bytes": [_i32, _i32],
+    "ivh_rerank_lists": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "ivh_scatter_pair_scores": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp],
+    "ivh_retrieval_ranks": [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp],
     "ivh_probe_cu_hog": [_vp, _vp, _i64, _i32, _vp],
     "ivh_probe_tr16": [_vp, _vp, _vp],
     "ivh_probe_mfma16": [_vp, _vp, _vp, _vp],
@@ -162,7 +168,7 @@ SIGNATURES = {
     "ivh_probe_attn32_fwd_qkn": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
                                  _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
 }
-_RESTYPES = {"ivh_last_error": C.c_char_p, "ivh_vtc_workspace_floats": C.c_int64, "ivh_gemm_split_workspace": C.c_int64, "ivh_gemm_fp8_split_workspace": C.c_int64,
+_RESTYPES = {"ivh_last_error": C.c_char_p, "ivh_vtc_workspace_floats": C.c_int64, "ivh_rerank_lists_workspace_bytes": C.c_int64, "ivh_gemm_split_workspace": C.c_int64, "ivh_gemm_fp8_split_workspace": C.c_int64,
              "ivh_gemm256_half_rounds": C.c_double}
 
 _lib: Optional[C.CDLL] = None

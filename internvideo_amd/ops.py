@@ -1321,6 +1321,101 @@ def abt_f32(a: torch.Tensor, b: torch.Tensor, alpha: float = 1.0) -> torch.Tenso
     return out
 
 
+# ---- stage-2 retrieval evaluation (csrc/retrieval.hip) ------------------------------------------------------------------------
+def _mat_f32(t: torch.Tensor, name: str) -> torch.Tensor:
+    """a 2-D fp32 matrix in HBM, any non-negative strides (the kernels take a row and a column stride: `.T` is a view, never a copy)"""
+    _chk(t, F32, name, inner_contig=False)
+    if t.dim() != 2 or t.numel() == 0:
+        raise InternVideoHipError(f"{name} must be a non-empty 2-D matrix, got {tuple(t.shape)}")
+    return t
+
+
+def _i32_dense(t: torch.Tensor, name: str) -> torch.Tensor:
+    _chk(t, torch.int32, name)
+    if not t.is_contiguous():
+        raise InternVideoHipError(f"{name} must be contiguous")
+    return t
+
+
+def topk_rows(x: torch.Tensor, k: int):
+    """x fp32 [R, C] (any strides) -> (values fp32 [R, k], indices int32 [R, k]): the k largest of every row, descending, ties by
+    ascending column"""
+    _L.require_gpu()
+    _mat_f32(x, "x")
+    R, Cn = x.shape
+    val = torch.empty((R, k), dtype=F32, device=x.device)
+    idx = torch.empty((R, k), dtype=torch.int32, device=x.device)
+    call("ivh_topk_rows_f32", ptr(x), R, Cn, x.stride(0), x.stride(1), int(k), ptr(val), ptr(idx), stream_ptr())
+    return val, idx
+
+
+def softmax_axis(x: torch.Tensor, mul_input: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """softmax over dim 1 of x fp32 [R, C] (any strides; pass `s.T` for a softmax over dim 0 of s), times x when mul_input"""
+    _L.require_gpu()
+    _mat_f32(x, "x")
+    R, Cn = x.shape
+    if out is None:
+        out = torch.empty((R, Cn), dtype=F32, device=x.device)
+    else:
+        _mat_f32(out, "out")
+        if out.shape != x.shape:
+            raise InternVideoHipError(f"softmax_axis: out {tuple(out.shape)} vs x {tuple(x.shape)}")
+    call("ivh_softmax_axis_f32", ptr(x), R, Cn, x.stride(0), x.stride(1), ptr(out), out.stride(0), out.stride(1), int(bool(mul_input)),
+         stream_ptr())
+    return out
+
+
+def rerank_lists(idx_v2t: torch.Tensor, idx_t2v: torch.Tensor, v_begin: int = 0, v_end: Optional[int] = None):
+    """idx_v2t int32 [nv, kv], idx_t2v int32 [nt, kt] -> (ptr int32 [n + 1], cand int32 [capacity], flags uint8 [capacity]) for the
+    videos [v_begin, v_end): CSR lists of the texts to score against each video (ascending, each once; flags bit 0 = the video chose the
+    text, bit 1 = the text chose the video).  Only the first ptr[-1] slots of cand / flags are written."""
+    _L.require_gpu()
+    _i32_dense(idx_v2t, "idx_v2t"); _i32_dense(idx_t2v, "idx_t2v")
+    if idx_v2t.dim() != 2 or idx_t2v.dim() != 2:
+        raise InternVideoHipError("rerank_lists: index matrices must be 2-D")
+    (nv, kv), (nt, kt) = idx_v2t.shape, idx_t2v.shape
+    v_end = nv if v_end is None else int(v_end)
+    n = v_end - int(v_begin)
+    cap = max(n, 0) * kv + nt * kt
+    dev = idx_v2t.device
+    ptr_ = torch.empty((max(n, 0) + 1,), dtype=torch.int32, device=dev)
+    cand = torch.empty((cap,), dtype=torch.int32, device=dev)
+    flags = torch.empty((cap,), dtype=torch.uint8, device=dev)
+    ws = torch.empty((max(int(_L.load().ivh_rerank_lists_workspace_bytes(max(n, 0), nt)), 4),), dtype=torch.uint8, device=dev)
+    call("ivh_rerank_lists", ptr(idx_v2t), nv, kv, ptr(idx_t2v), nt, kt, int(v_begin), v_end, ptr(ptr_), ptr(cand), ptr(flags), ptr(ws),
+         stream_ptr())
+    return ptr_, cand, flags
+
+
+def scatter_pair_scores(ptr_: torch.Tensor, cand: torch.Tensor, flags: torch.Tensor, scores: torch.Tensor, v_begin: int,
+                        x_v2t: torch.Tensor, x_t2v: torch.Tensor) -> None:
+    """scores fp32 [capacity] (one per cand entry) -> x_v2t[i, j] where bit 0 of the entry's flag is set, x_t2v[j, i] where bit 1 is;
+    no other element of x_v2t fp32 [nv, nt] / x_t2v fp32 [nt, nv] is touched"""
+    _L.require_gpu()
+    _i32_dense(ptr_, "ptr"); _i32_dense(cand, "cand"); _chk(flags, torch.uint8, "flags"); _chk(scores, F32, "scores")
+    _mat_f32(x_v2t, "x_v2t"); _mat_f32(x_t2v, "x_t2v")
+    nv, nt = x_v2t.shape
+    if tuple(x_t2v.shape) != (nt, nv):
+        raise InternVideoHipError(f"scatter_pair_scores: x_t2v {tuple(x_t2v.shape)} is not the transpose shape of x_v2t {tuple(x_v2t.shape)}")
+    if not (flags.is_contiguous() and scores.is_contiguous()) or flags.numel() != cand.numel() or scores.numel() != cand.numel():
+        raise InternVideoHipError("scatter_pair_scores: cand, flags and scores must be dense and of one length")
+    call("ivh_scatter_pair_scores", ptr(ptr_), ptr(cand), ptr(flags), ptr(scores), cand.numel(), int(v_begin), ptr_.numel() - 1, nv, nt,
+         ptr(x_v2t), x_v2t.stride(0), x_v2t.stride(1), ptr(x_t2v), x_t2v.stride(0), x_t2v.stride(1), stream_ptr())
+
+
+def retrieval_ranks(scores: torch.Tensor, gt_ptr: torch.Tensor, gt_idx: torch.Tensor) -> torch.Tensor:
+    """scores fp32 [R, C] (any strides), ground truths in CSR form (gt_ptr int32 [R + 1], gt_idx int32) -> rank int32 [R]: the best
+    position of a ground-truth column in the row's descending order (ties: lower column first)"""
+    _L.require_gpu()
+    _mat_f32(scores, "scores"); _i32_dense(gt_ptr, "gt_ptr"); _i32_dense(gt_idx, "gt_idx")
+    R, Cn = scores.shape
+    if gt_ptr.numel() != R + 1:
+        raise InternVideoHipError(f"retrieval_ranks: gt_ptr has {gt_ptr.numel()} entries for {R} rows")
+    rank = torch.empty((R,), dtype=torch.int32, device=scores.device)
+    call("ivh_retrieval_ranks", ptr(scores), R, Cn, scores.stride(0), scores.stride(1), ptr(gt_ptr), ptr(gt_idx), ptr(rank), stream_ptr())
+    return rank
+
+
 # ---- probes ---------------------------------------------------------------------------------------------------------------
 def probe_tr16(inp: torch.Tensor) -> torch.Tensor:
     _L.require_gpu()

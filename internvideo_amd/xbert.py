@@ -13,7 +13,8 @@ All arithmetic is in libinternvideo_hip.so:
   q, k, v            one MFMA GEMM on the concatenated weights -> packed [B*L, 3*D] rows, read in place by the attention kernels
   attention          ivh_flash_attn_fwd / _bwd with kv_len (right-padded text; the reference adds -10000 to the padded keys' scores,
                      xbert.py:1118-1120, which removes them from an fp32 softmax exactly) -- self (Lq = Lk = L) and cross (keys / values
-                     from the vision tokens, width `encoder_width`)
+                     from the vision tokens, width `encoder_width`; encoder states of batch 1 are shared by the whole text batch: K / V
+                     projected once, the B * L query rows as one sequence -- inference only, retrieval re-ranking)
   dense + LayerNorm  GEMM (+ bias) then ivh_add_layernorm_fwd / _bwd: LayerNorm(dense + residual) on bf16 rows, fp32 statistics
   feed-forward       fc1 GEMM with erf-GELU epilogue (gelu' as by-product), fc2 GEMM whose dgrad epilogue multiplies by gelu'
   MLM / VTM heads    decoder GEMM on the (tied) word-embedding matrix padded to a multiple of 8 columns, ivh_ce_rows for the loss and,
@@ -338,6 +339,17 @@ class BertSelfAttention(nn.Module):
                                     self.value.weight, self.value.bias)
             return SelfAttnFn.apply(qkv, B, L, H, kv_len, *drop).view(B, L, D)
         Lk = encoder_hidden_states.shape[1]
+        if encoder_hidden_states.shape[0] == 1 and B > 1:
+            # ONE set of encoder states shared by the B texts (retrieval re-ranking: the candidate texts of one video).  Keys and values
+            # are projected once; non-causal cross-attention treats every query row on its own, so the B * L query rows run as one
+            # sequence against them -- the same arithmetic per row as with B copies of the encoder states.  Inference only.
+            if torch.is_grad_enabled() or drop[0]:
+                raise InternVideoHipError("cross-attention against shared encoder states (encoder batch 1, text batch > 1) is an inference "
+                                          "pass: call it in eval mode under torch.no_grad()")
+            q = Fn.LinearFn.apply(hidden_states, self.query.weight, self.query.bias).view(1, B * L, H, hd)
+            k = Fn.LinearFn.apply(encoder_hidden_states, self.key.weight, self.key.bias).view(1, Lk, H, hd)
+            v = Fn.LinearFn.apply(encoder_hidden_states, self.value.weight, self.value.bias).view(1, Lk, H, hd)
+            return ops.flash_attn_fwd(q, k, v, kv_len=encoder_kv_len)[0].view(B, L, D)
         q = Fn.LinearFn.apply(hidden_states, self.query.weight, self.query.bias).view(B, L, H, hd)
         k = Fn.LinearFn.apply(encoder_hidden_states, self.key.weight, self.key.bias).view(B, Lk, H, hd)
         v = Fn.LinearFn.apply(encoder_hidden_states, self.value.weight, self.value.bias).view(B, Lk, H, hd)
