@@ -28,7 +28,8 @@ int ivh_version(void);
  *       new entry points ivh_droppath_plan, ivh_rmsnorm_add_{fwd,bwd}_skip, ivh_colsum_finish_dyn, ivh_qk_rmsnorm_{fwd,bwd}_dyn,
  *       ivh_flash_attn_{fwd,bwd}_dyn.  Every signature of ABI 1 (as of round 5) is unchanged.
  *       Added since, without a version step (additions only): ivh_mix_clips, ivh_soft_ce_rows, ivh_mixup_target; ivh_topk_rows_f32,
- *       ivh_softmax_axis_f32, ivh_rerank_lists (+ ivh_rerank_lists_workspace_bytes), ivh_scatter_pair_scores, ivh_retrieval_ranks. */
+ *       ivh_softmax_axis_f32, ivh_rerank_lists (+ ivh_rerank_lists_workspace_bytes), ivh_scatter_pair_scores, ivh_retrieval_ranks;
+ *       ivh_cat_pool_{fwd,bwd}, ivh_batchnorm_cols_{fwd,bwd}. */
 #define IVH_ABI_VERSION 2
 int ivh_abi_version(void);
 /* Device-side dropout epoch.  The dropout masks of ivh_bert_embed_*, ivh_add_layernorm_* and ivh_flash_attn_*_dropout are counter based:
@@ -584,6 +585,32 @@ int ivh_scatter_pair_scores(const int32_t* ptr, const int32_t* cand, const uint8
  * without a ground truth inside the matrix.  Equal to the reference on rows without ties.  gt_ptr int32 [n_rows + 1], non-decreasing. */
 int ivh_retrieval_ranks(const float* scores, int n_rows, int n_cols, int64_t row_stride, int64_t col_stride, const int32_t* gt_ptr,
                         const int32_t* gt_idx, int32_t* rank, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Linear / attentive probing heads (models/internvideo2_cat.py "C:", run_linear_probing.py).  Arguments are checked on the host (< 0, nothing
+ * launched), the work goes on `stream`, no float atomics: two runs on the same inputs agree bit for bit. */
+/* `cls, avg = x[:, :1], x[:, 1:]; avg.view(B, T, S, C).mean(2)` (mode 0, avgN: out fp32 [B][1 + T][C]) or `avg.mean(1)` (mode 1, avg1:
+ * out fp32 [B][2][C]) of the final residual stream x [B][1 + T*S][C] (fp32, or bf16 when x_fp32 == 0), C:583-587; row 0 of every clip is
+ * the cls row.  tokmean (optional, fp32 [B][C]): `x.mean(1)` over all 1 + T*S tokens, the query AttentionPoolingBlock builds (P:110), from
+ * the same pass.  ws: fp32 [B][T][C] workspace, needed in mode 1 only.  C % 8 == 0, pointers 16-byte aligned. */
+int ivh_cat_pool_fwd(const void* x, int x_fp32, int B, int T, int S, int C, int mode, float* out, float* tokmean, float* ws, void* stream);
+/* the stream gradient of the above: dx fp32 [B][1 + T*S][C] = (accumulate ? dx : 0) + d cls on row 0, + d mean / S (mode 1: / (T S)) on the
+ * patch rows, + dtokmean / (1 + T*S) on every row.  dout [B][G][C] or dtokmean [B][C] may be NULL (not both).  C % 4 == 0. */
+int ivh_cat_pool_bwd(const float* dout, const float* dtokmean, int B, int T, int S, int C, int mode, int accumulate, float* dx, void* stream);
+/* `down_norm(final.permute(0, 2, 1)).reshape(B, -1)` (C:589-590) with down_norm = BatchNorm1d(C) (C:443-448): x [B][G][C] (fp32 or bf16),
+ * statistics over the B * G values of a channel, y bf16 [B][ld_y] with y[b][c * G + g] (channel-major, as the head reads it; ld_y >= C * G).
+ * training != 0: centred fp32 statistics (mean, then squared deviations), biased variance to normalise; save_mean / save_rstd fp32 [C];
+ * running_mean / running_var (both or neither) updated IN DEVICE MEMORY with `momentum` and the unbiased variance, *num_batches_tracked
+ * (int64, optional) += 1 -- a step captured into a HIP graph updates them on every replay.  B * G > 1.
+ * training == 0: normalises with the running buffers (which are left alone; save_* receive the values used).  w / b: affine, or NULL. */
+int ivh_batchnorm_cols_fwd(const void* x, int x_fp32, int B, int G, int C, const float* w, const float* b, float eps, int training,
+                           float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, uint16_t* y, int64_t ld_y,
+                           float* save_mean, float* save_rstd, void* stream);
+/* its backward: dy bf16 [B][ld_dy] in the flattened layout; dx [B][G][C] (fp32 when dx_fp32, else bf16) = rstd w (dy - mean(dy) - xhat
+ * mean(dy xhat)) (training == 0: rstd w dy), times dact[b][g][c] (bf16, optional: the GELU derivative of the `down` projection, C:457-460);
+ * dw / db fp32 [C] (optional) = sum dy xhat / sum dy, overwritten. */
+int ivh_batchnorm_cols_bwd(const void* x, int x_fp32, int B, int G, int C, const float* w, const float* mean, const float* rstd, int training,
+                           const uint16_t* dy, int64_t ld_dy, const uint16_t* dact, void* dx, int dx_fp32, float* dw, float* db, void* stream);
 
 #ifdef __cplusplus
 }

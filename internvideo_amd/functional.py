@@ -1041,13 +1041,19 @@ class AttnPoolFn(torch.autograd.Function):
     bias parameters, 1-query multi-head attention (the flash kernel with Lq = 1), output projection."""
 
     @staticmethod
-    def forward(ctx, x, B, L, H, ln_eps, nqw, nqb, nkw, nkb, nvw, nvb, qw, qb, kw, kb, vw, vb, pw, pb):
+    def forward(ctx, x, B, L, H, ln_eps, nqw, nqb, nkw, nkb, nvw, nvb, qw, qb, kw, kb, vw, vb, pw, pb, xm=None):
+        """xm (optional, fp32 [B, D]): the all-token mean of x when the caller already has it (probe.ProbePoolFn takes it from the pass that
+        pools the stream for the concatenating heads); its gradient then goes back to that caller instead of into dx"""
         D = x.shape[-1]
         hd = D // H
         ctx.xdtype = x.dtype
         if x.dtype != F32:                                                      # a bf16 tap of the residual stream: this block works on fp32 rows
             x = x.float()
-        xm = ops.token_mean_fwd(x, B, L)                                        # [B, D] fp32
+        ctx.xm_given = xm is not None
+        if xm is None:
+            xm = ops.token_mean_fwd(x, B, L)                                    # [B, D] fp32
+        else:
+            xm = xm.detach().reshape(B, D).float().contiguous()
         qin, _, qstats = ops.layernorm_fwd(xm, vec(nqw), vec(nqb), ln_eps)
         kin, vin, kvstats = ops.layernorm_fwd(x, vec(nkw), vec(nkb), ln_eps, vec(nvw), vec(nvb))
         q = ops.gemm(qin, mat(qw), bias=vec(qb))                                # [B, D]
@@ -1092,14 +1098,15 @@ class AttnPoolFn(torch.autograd.Function):
         gvw = _wgrad_defer(dv, vin, vw); gvb = _ret_grad(vb, _vgrad(vb, ops.colsum_bf16(dv)))
         dx, dnkw, dnkb, dnvw, dnvb = ops.layernorm_bwd(x, vec(nkw), kvstats, dkin, vec(nvw), dvin)
         dxm, dnqw, dnqb, _, _ = ops.layernorm_bwd(xm, vec(nqw), qstats, dqin)
-        ops.token_mean_bwd(dxm, dx, B, L)
+        if not ctx.xm_given:
+            ops.token_mean_bwd(dxm, dx, B, L)
         if dx.dtype != ctx.xdtype:
             dx = dx.to(ctx.xdtype)
         return (dx, None, None, None, None,
                 _ret_grad(nqw, _vgrad(nqw, dnqw)), _ret_grad(nqb, _vgrad(nqb, dnqb)),
                 _ret_grad(nkw, _vgrad(nkw, dnkw)), _ret_grad(nkb, _vgrad(nkb, dnkb)),
                 _ret_grad(nvw, _vgrad(nvw, dnvw)), _ret_grad(nvb, _vgrad(nvb, dnvb)),
-                gqw, gqb, gkw, gkb, gvw, gvb, gpw, gpb)
+                gqw, gqb, gkw, gkb, gvw, gvb, gpw, gpb, (dxm if ctx.xm_given else None))
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1149,15 +1156,20 @@ def frozen_fp8_weight(w: torch.Tensor):
 
 
 @torch.no_grad()
-def block_stack_infer(x0, block_params: Sequence, S: int, L: int, H: int, eps: float, act: str, taps: Sequence[int], fp8: bool = False):
+def block_stack_infer(x0, block_params: Sequence, S: int, L: int, H: int, eps: float, act: str, taps: Sequence[int], fp8: bool = False,
+                      rowscale: Optional[torch.Tensor] = None):
     """The fused-residual block loop of BlockStackFn.forward without the autograd bookkeeping.  block_params: per block the 13
     tensors of Block.flat_params().  -> {tap index: fp32 [S*L, D] residual-stream value after that block}; the last block is
     always tapped.  fp8 (opt-in, frozen teachers only): the four GEMMs of every block on the e4m3 MFMA path -- activations quantised per
-    tensor on the fly, weights once with per-channel scales (frozen_fp8_weight); norms, attention and the residual stream unchanged."""
+    tensor on the fly, weights once with per-channel scales (frozen_fp8_weight); norms, attention and the residual stream unchanged.
+    rowscale (fp32 [depth, 2, S], optional): the per-(block, branch, sample) DropPath factors of BlockStackFn, multiplied into the residual
+    adds (no sample is skipped) -- a frozen prefix of a model in train mode applies its DropPath draws as the reference does (probe.py)."""
     depth = len(block_params)
+    if rowscale is not None and tuple(rowscale.shape) != (depth, 2, S):
+        raise ValueError(f"rowscale {tuple(rowscale.shape)}: expected {(depth, 2, S)}")
     want = set(taps) | {depth - 1}
     outs = {}
-    res, branch, g_prev = x0, None, None
+    res, branch, g_prev, rs_prev = x0, None, None, None
     def lin(x, w, bias=None, act=None):
         if not fp8:
             return ops.gemm(x, mat(w), bias=bias, act=act)
@@ -1171,7 +1183,7 @@ def block_stack_infer(x0, block_params: Sequence, S: int, L: int, H: int, eps: f
             res1 = res
             _, n1, _ = ops.rmsnorm_add_fwd(res, None, None, None, L, vec(n1w), eps, want_res_out=False)
         else:
-            res1, n1, _ = ops.rmsnorm_add_fwd(res, branch, g_prev, None, L, vec(n1w), eps)
+            res1, n1, _ = ops.rmsnorm_add_fwd(res, branch, g_prev, rs_prev, L, vec(n1w), eps)
             if (i - 1) in want:
                 outs[i - 1] = res1
         qkv = lin(n1, qkvw)
@@ -1181,14 +1193,15 @@ def block_stack_infer(x0, block_params: Sequence, S: int, L: int, H: int, eps: f
         del qkv
         b1 = lin(att, projw, bias=vec(projb))
         del att
-        res2, n2, _ = ops.rmsnorm_add_fwd(res1, b1, vec(ls1) if ls1 is not None else None, None, L, vec(n2w), eps)
+        res2, n2, _ = ops.rmsnorm_add_fwd(res1, b1, vec(ls1) if ls1 is not None else None, rowscale[i, 0] if rowscale is not None else None,
+                                          L, vec(n2w), eps)
         del b1
         g = lin(n2, fc1w, bias=vec(fc1b), act=_act_d(act))   # (no gelu' copy is asked for: the exchanged flavours are the ones the 256^2 kernels carry)
         del n2
         branch = lin(g, fc2w, bias=vec(fc2b))
         del g
-        res, g_prev = res2, (vec(ls2) if ls2 is not None else None)
-    final, _, _ = ops.rmsnorm_add_fwd(res, branch, g_prev, None, L, None, eps)
+        res, g_prev, rs_prev = res2, (vec(ls2) if ls2 is not None else None), (rowscale[i, 1] if rowscale is not None else None)
+    final, _, _ = ops.rmsnorm_add_fwd(res, branch, g_prev, rs_prev, L, None, eps)
     outs[depth - 1] = final
     return outs
 

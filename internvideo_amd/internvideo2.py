@@ -17,7 +17,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import functional as Fn
-from .internvideo2_pretrain import AttentionPoolingBlock, Block, PatchEmbed, PretrainInternVideo2, RMSNorm, _trunc_normal_, register_model
+from .internvideo2_pretrain import AttentionPoolingBlock, Block, PatchEmbed, PretrainInternVideo2, RMSNorm, _residual_is_bf16, _trunc_normal_, register_model
 
 
 class PaddedHeadFn(torch.autograd.Function):
@@ -121,17 +121,78 @@ class InternVideo2(PretrainInternVideo2):
     def no_weight_decay(self):                                                                   # F:490-498
         return {'pos_embed', 'pos_embed_spatial', 'pos_embed_temporal', 'pos_embed_cls', 'cls_token'}
 
-    def forward(self, x):
-        """F:500-543 -> logits (B, num_classes) bf16"""
-        taps, _, _, B, L = self.forward_features(x, None)
-        pooled = self.clip_projector(taps[self.depth - 1], B, L)                                 # F:538
-        h = Fn.LayerNormFn.apply(pooled, self.fc_norm.weight, self.fc_norm.bias, self.fc_norm.eps)   # F:539
+    def _frozen_prefix(self, x) -> int:
+        """how many leading blocks run forward-only (probe.freeze_for_probing sets `frozen_prefix`): 0 without the attribute; every block
+        when no gradient is recorded; else the attribute's n, provided the prefix really is frozen -- every parameter of blocks < n and of
+        the embedding (patch embed, cls token, positional tables) has requires_grad False and the clip itself needs no gradient.  The
+        forward-only loop is the fp32-stream bf16 one: a model with fp8 GEMMs or a bf16 residual stream keeps the autograd stack."""
+        n = int(getattr(self, "frozen_prefix", 0) or 0)
+        if n <= 0 or getattr(self, "fp8_gemm", False) or _residual_is_bf16(getattr(self, "residual_dtype", "fp32")):
+            return 0
+        if not torch.is_grad_enabled():
+            return self.depth
+        n = min(n, self.depth)
+        if x.requires_grad:
+            return 0
+        embed = [p for name, p in self.named_parameters(recurse=False) if name == "cls_token" or name.startswith("pos_embed")]
+        embed += list(self.patch_embed.parameters())
+        for blk in self.blocks[:n]:
+            embed += list(blk.parameters())
+        return 0 if any(p.requires_grad for p in embed) else n
+
+    def _final_stream(self, x):
+        """-> (the residual stream after the last block and the final `x + residual` (F:527-536), fp32 [B*L, D]; B; L).  With a frozen
+        prefix of n blocks (`_frozen_prefix`) the patch embed and blocks 0 .. n-1 run through the forward-only loop (nothing is saved) and
+        blocks n .. depth-1 through BlockStackFn, which starts from the prefix's last tap: the same residual-stream value, since the
+        first block of a stack reads `res = x0, branch = None`.  DropPath draws are taken for the whole depth either way."""
+        n = self._frozen_prefix(x)
+        if n == 0:
+            taps, _, _, B, L = self.forward_features(x, None)
+            return taps[self.depth - 1], B, L
+        if not x.is_cuda:
+            raise Fn.ops.InternVideoHipError("InternVideo2.forward needs HBM-resident inputs: there is no CPU path")
+        if x.dim() != 5:
+            raise ValueError(f"expected a (B, C, T, H, W) clip tensor, got {tuple(x.shape)}")
+        pe = self.patch_embed
+        x0, B, L = Fn.embed_all_tokens(x, pe.proj.weight, pe.proj.bias, self.cls_token, self._pos_table("").detach(), pe.tubelet_size, pe.patch_size[0])
+        rs = self._drop_path_scales(B, x.device)
+        outs = Fn.block_stack_infer(x0, [blk.flat_params() for blk in self.blocks[:n]], B, L, self.num_heads, 1e-6, self.fused_mlp_act, (),
+                                    rowscale=(rs[:n] if rs is not None else None))
+        xn = outs[n - 1]
+        if n == self.depth:
+            return xn, B, L
+        n_cp = 0
+        for blk in self.blocks[n:]:
+            if not getattr(blk, "with_cp", False):
+                break
+            n_cp += 1
+        hook = self.grad_ready_hook                      # the engine counts blocks from the bottom of the model, the suffix stack from its own
+        meta = dict(B=B, L=L, H=self.num_heads, eps=1e-6, act=self.fused_mlp_act, taps=[self.depth - 1 - n],
+                    grad_ready_hook=(None if hook is None else (lambda i, _h=hook, _n=n: _h(i + _n))), checkpoint_num=n_cp, fp8=False,
+                    fp8_hist=None, fp8_wchan=False, res_bf16=False, taps_bf16=False,
+                    dp_skip=getattr(self, "drop_path_skip", "auto"), dp_count_acc=None)
+        params = [p for blk in self.blocks[n:] for p in blk.flat_params()]
+        (final,) = Fn.BlockStackFn.apply(xn, rs[n:].contiguous() if rs is not None else None, meta, *params)
+        return final, B, L
+
+    def _pooled_features(self, xf, B, L, token_mean=None):
+        """fc_norm(clip_projector(x)) (F:538-539) -> bf16 (B, clip_embed_dim); token_mean: see AttentionPoolingBlock.forward"""
+        pooled = self.clip_projector(xf, B, L, token_mean)                                       # F:538
+        return Fn.LayerNormFn.apply(pooled, self.fc_norm.weight, self.fc_norm.bias, self.fc_norm.eps)   # F:539
+
+    def _classify(self, h):
+        """head(fc_dropout(h)) (F:540-541)"""
         h = self.fc_dropout(h)                                                                   # F:540 (a (B, 768) tensor)
         w, b = self.head.weight, self.head.bias
         n = w.shape[0]
         if n % 8:                                          # class counts like 174 / 339: the GEMM moves 8-column chunks -> zero-pad
             return PaddedHeadFn.apply(h, w, b)
         return Fn.LinearFn.apply(h, w, b)[:, :n]
+
+    def forward(self, x):
+        """F:500-543 -> logits (B, num_classes) bf16"""
+        xf, B, L = self._final_stream(x)
+        return self._classify(self._pooled_features(xf, B, L))
 
     def forward_loss(self, x, target, target_b=None, mix=None, smoothing: float = 0.0):
         """the fine-tuning step's loss (engines/engine_for_finetuning.py:13-17 with the criterion of run_finetuning.py:593-599) in one

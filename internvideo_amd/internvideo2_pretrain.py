@@ -211,13 +211,15 @@ class AttentionPoolingBlock(nn.Module):
         self.cross_attn = CrossAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, out_dim=out_dim)
         self.num_heads = num_heads
 
-    def forward(self, x, B, L):
-        """x: fp32 residual-stream rows [B*L, D] -> [B, out_dim] bf16"""
+    def forward(self, x, B, L, token_mean=None):
+        """x: fp32 residual-stream rows [B*L, D] -> [B, out_dim] bf16.  token_mean (optional, fp32 [B, D]): x.mean over the L tokens, when
+        the caller has it already"""
         ca = self.cross_attn
-        return Fn.AttnPoolFn.apply(x, B, L, self.num_heads, self.norm1_q.eps,
-                                   self.norm1_q.weight, self.norm1_q.bias, self.norm1_k.weight, self.norm1_k.bias,
-                                   self.norm1_v.weight, self.norm1_v.bias, ca.q.weight, ca.q_bias, ca.k.weight, ca.k_bias,
-                                   ca.v.weight, ca.v_bias, ca.proj.weight, ca.proj.bias)
+        args = (x, B, L, self.num_heads, self.norm1_q.eps,
+                self.norm1_q.weight, self.norm1_q.bias, self.norm1_k.weight, self.norm1_k.bias,
+                self.norm1_v.weight, self.norm1_v.bias, ca.q.weight, ca.q_bias, ca.k.weight, ca.k_bias,
+                ca.v.weight, ca.v_bias, ca.proj.weight, ca.proj.bias)
+        return Fn.AttnPoolFn.apply(*args) if token_mean is None else Fn.AttnPoolFn.apply(*args, token_mean)
 
 
 class Linear_Decoder(nn.Module):

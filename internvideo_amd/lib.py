@@ -157,6 +157,10 @@ SIGNATURES = {
     "ivh_rerank_lists": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "ivh_scatter_pair_scores": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp, _i64, _i64, _vp],
     "ivh_retrieval_ranks": [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp],
+    "ivh_cat_pool_fwd": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "ivh_cat_pool_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "ivh_batchnorm_cols_fwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
+    "ivh_batchnorm_cols_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
     "ivh_probe_cu_hog": [_vp, _vp, _i64, _i32, _vp],
     "ivh_probe_tr16": [_vp, _vp, _vp],
     "ivh_probe_mfma16": [_vp, _vp, _vp, _vp],

@@ -1453,3 +1453,127 @@ def probe_mfma_rate2(shape: int, waves_per_simd: int, iters: int, workgroups: in
     sink = torch.zeros((1,), dtype=F32, device="cuda")
     call("ivh_probe_mfma_rate2", int(shape), int(waves_per_simd), int(iters), int(workgroups), ptr(sink), stream_ptr())
     return 262144.0 * iters * 4 * waves_per_simd * workgroups
+
+
+# ---- linear / attentive probing heads (csrc/probe.hip) -------------------------------------------------------------------------
+def _stream_rows(x: torch.Tensor, B: int, T: int, S: int, name: str) -> int:
+    if x.dtype not in (F32, BF16):
+        raise InternVideoHipError(f"{name} must be fp32 or bf16 (got {x.dtype})")
+    _chk_rows(x, x.dtype, name)
+    L = 1 + int(T) * int(S)
+    if B <= 0 or T <= 0 or S <= 0 or x.numel() % (B * L) or x.numel() == 0:
+        raise InternVideoHipError(f"{name}: {tuple(x.shape)} is not B = {B} clips of 1 + {T} * {S} rows")
+    return x.numel() // (B * L)
+
+
+def cat_pool_fwd(x: torch.Tensor, B: int, T: int, S: int, avg1: bool = False, want_token_mean: bool = False):
+    """x: the final residual stream, [B * (1 + T*S), C] fp32 | bf16 -> (out fp32 [B, G, C]: row 0 the cls row, then the T per-frame patch
+    means (G = 1 + T) or, `avg1`, the one patch mean (G = 2); tokmean fp32 [B, C] | None: the mean over all 1 + T*S tokens)"""
+    _L.require_gpu()
+    Cn = _stream_rows(x, B, T, S, "x")
+    G = 2 if avg1 else 1 + T
+    out = torch.empty((B, G, Cn), dtype=F32, device=x.device)
+    tok = torch.empty((B, Cn), dtype=F32, device=x.device) if want_token_mean else None
+    ws = torch.empty((B, T, Cn), dtype=F32, device=x.device) if avg1 else None
+    _pcall("cat_pool_fwd", x.numel() * x.element_size(), "B", "ivh_cat_pool_fwd", ptr(x), int(x.dtype == F32), int(B), int(T), int(S), Cn,
+           int(bool(avg1)), ptr(out), ptr(tok), ptr(ws), stream_ptr())
+    return out, tok
+
+
+def cat_pool_bwd(dout: Optional[torch.Tensor], dtokmean: Optional[torch.Tensor], B: int, T: int, S: int, avg1: bool = False,
+                   dx: Optional[torch.Tensor] = None, accumulate: bool = False) -> torch.Tensor:
+    """gradient of cat_pool_fwd w.r.t. the stream: dout fp32 [B, G, C] | None, dtokmean fp32 [B, C] | None -> dx fp32 [B * (1 + T*S), C]
+    (written, or added to the given `dx` when `accumulate`)"""
+    _L.require_gpu()
+    ref = dout if dout is not None else dtokmean
+    if ref is None:
+        raise InternVideoHipError("cat_pool_bwd: neither dout nor dtokmean")
+    Cn = ref.shape[-1]
+    G = 2 if avg1 else 1 + T
+    if dout is not None:
+        _chk_rows(dout, F32, "dout")
+        if tuple(dout.shape) != (B, G, Cn):
+            raise InternVideoHipError(f"cat_pool_bwd: dout {tuple(dout.shape)}, expected {(B, G, Cn)}")
+    if dtokmean is not None:
+        _chk_rows(dtokmean, F32, "dtokmean")
+        if tuple(dtokmean.shape) != (B, Cn):
+            raise InternVideoHipError(f"cat_pool_bwd: dtokmean {tuple(dtokmean.shape)}, expected {(B, Cn)}")
+    L = 1 + int(T) * int(S)
+    if dx is None:
+        dx = torch.empty((B * L, Cn), dtype=F32, device=ref.device)
+        accumulate = False
+    else:
+        _chk_rows(dx, F32, "dx")
+        if dx.numel() != B * L * Cn:
+            raise InternVideoHipError(f"cat_pool_bwd: dx holds {dx.numel()} elements, expected {B * L * Cn}")
+    _pcall("cat_pool_bwd", dx.numel() * 4 * (2 if accumulate else 1), "B", "ivh_cat_pool_bwd", ptr(dout), ptr(dtokmean), int(B), int(T),
+           int(S), Cn, int(bool(avg1)), int(bool(accumulate)), ptr(dx), stream_ptr())
+    return dx
+
+
+def _bn_vec(t: Optional[torch.Tensor], Cn: int, name: str) -> Optional[torch.Tensor]:
+    if t is None:
+        return None
+    _chk(t, F32, name)
+    if t.numel() != Cn or not t.is_contiguous():
+        raise InternVideoHipError(f"{name} must be a contiguous fp32 [{Cn}] tensor")
+    return t
+
+
+def batchnorm_cols_fwd(x: torch.Tensor, w: Optional[torch.Tensor], b: Optional[torch.Tensor], eps: float, training: bool,
+                       momentum: float = 0.1, running_mean: Optional[torch.Tensor] = None, running_var: Optional[torch.Tensor] = None,
+                       num_batches_tracked: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+    """x [B, G, C] fp32 | bf16 -> (y bf16 [B, C * G] with y[b, c * G + g]: BatchNorm1d over the B * G values of a channel, written in the
+    layout `down_norm(x.permute(0, 2, 1)).reshape(B, -1)` has; mean fp32 [C]; rstd fp32 [C]).  training: batch statistics, and the running
+    buffers / the int64 counter are updated on the device; else the running buffers normalise.  out: a bf16 [B, >= C * G] destination whose
+    first C * G columns are written (row pitch out.stride(0))."""
+    _L.require_gpu()
+    if x.dtype not in (F32, BF16) or x.dim() != 3:
+        raise InternVideoHipError(f"batchnorm_cols_fwd: x must be a [B, G, C] fp32 / bf16 tensor (got {x.dtype} {tuple(x.shape)})")
+    _chk_rows(x, x.dtype, "x")
+    B, G, Cn = x.shape
+    w, b = _bn_vec(w, Cn, "w"), _bn_vec(b, Cn, "b")
+    rm, rv = _bn_vec(running_mean, Cn, "running_mean"), _bn_vec(running_var, Cn, "running_var")
+    if num_batches_tracked is not None and (num_batches_tracked.dtype != torch.int64 or not num_batches_tracked.is_cuda or num_batches_tracked.numel() != 1):
+        raise InternVideoHipError("num_batches_tracked must be a 1-element int64 tensor in HBM")
+    if out is None:
+        out = torch.empty((B, Cn * G), dtype=BF16, device=x.device)
+    else:
+        _chk(out, BF16, "out")
+        if out.dim() != 2 or out.shape[0] != B or out.shape[1] < Cn * G:
+            raise InternVideoHipError(f"batchnorm_cols_fwd: out {tuple(out.shape)} cannot hold [{B}, {Cn * G}]")
+    mean = torch.empty((Cn,), dtype=F32, device=x.device)
+    rstd = torch.empty((Cn,), dtype=F32, device=x.device)
+    call("ivh_batchnorm_cols_fwd", ptr(x), int(x.dtype == F32), B, G, Cn, ptr(w), ptr(b), float(eps), int(bool(training)), float(momentum),
+         ptr(rm), ptr(rv), ptr(num_batches_tracked), ptr(out), out.stride(0) if B > 1 else max(out.stride(0), Cn * G), ptr(mean), ptr(rstd),
+         stream_ptr())
+    return out, mean, rstd
+
+
+def batchnorm_cols_bwd(x: torch.Tensor, w: Optional[torch.Tensor], mean: torch.Tensor, rstd: torch.Tensor, dy: torch.Tensor, training: bool = True,
+                       dact: Optional[torch.Tensor] = None, dx_dtype: torch.dtype = F32, want_affine_grads: bool = False,
+                       dw_out: Optional[torch.Tensor] = None, db_out: Optional[torch.Tensor] = None):
+    """dy bf16 [B, >= C * G] (flattened channel-major, row pitch dy.stride(0)) -> (dx [B, G, C] in dx_dtype, dw fp32 [C] | None,
+    db fp32 [C] | None).  dact (bf16 [B, G, C], optional) multiplies dx."""
+    _L.require_gpu()
+    B, G, Cn = x.shape
+    _chk_rows(x, x.dtype, "x")
+    _chk(dy, BF16, "dy")
+    if dy.dim() != 2 or dy.shape[0] != B or dy.shape[1] < Cn * G:
+        raise InternVideoHipError(f"batchnorm_cols_bwd: dy {tuple(dy.shape)} cannot hold [{B}, {Cn * G}]")
+    if dx_dtype not in (F32, BF16):
+        raise InternVideoHipError("batchnorm_cols_bwd: dx is fp32 or bf16")
+    w, mean, rstd = _bn_vec(w, Cn, "w"), _bn_vec(mean, Cn, "mean"), _bn_vec(rstd, Cn, "rstd")
+    if dact is not None:
+        _chk_rows(dact, BF16, "dact")
+        if dact.numel() != x.numel():
+            raise InternVideoHipError("batchnorm_cols_bwd: dact must have x's shape")
+    dx = torch.empty((B, G, Cn), dtype=dx_dtype, device=x.device)
+    dw = db = None
+    if want_affine_grads:
+        dw, db = _f32_vec(dw_out, Cn), _f32_vec(db_out, Cn)
+        dw = dw if dw is not None else torch.empty((Cn,), dtype=F32, device=x.device)
+        db = db if db is not None else torch.empty((Cn,), dtype=F32, device=x.device)
+    call("ivh_batchnorm_cols_bwd", ptr(x), int(x.dtype == F32), B, G, Cn, ptr(w), ptr(mean), ptr(rstd), int(bool(training)), ptr(dy),
+         dy.stride(0) if B > 1 else max(dy.stride(0), Cn * G), ptr(dact), ptr(dx), int(dx_dtype == F32), ptr(dw), ptr(db), stream_ptr())
+    return dx, dw, db
