@@ -29,7 +29,7 @@ int ivh_version(void);
  *       ivh_flash_attn_{fwd,bwd}_dyn.  Every signature of ABI 1 (as of round 5) is unchanged.
  *       Added since, without a version step (additions only): ivh_mix_clips, ivh_soft_ce_rows, ivh_mixup_target; ivh_topk_rows_f32,
  *       ivh_softmax_axis_f32, ivh_rerank_lists (+ ivh_rerank_lists_workspace_bytes), ivh_scatter_pair_scores, ivh_retrieval_ranks;
- *       ivh_cat_pool_{fwd,bwd}, ivh_batchnorm_cols_{fwd,bwd}. */
+ *       ivh_cat_pool_{fwd,bwd}, ivh_batchnorm_cols_{fwd,bwd}; ivh_eval_rows, ivh_view_finalize, ivh_view_mask_owned. */
 #define IVH_ABI_VERSION 2
 int ivh_abi_version(void);
 /* Device-side dropout epoch.  The dropout masks of ivh_bert_embed_*, ivh_add_layernorm_* and ivh_flash_attn_*_dropout are counter based:
@@ -611,6 +611,40 @@ int ivh_batchnorm_cols_fwd(const void* x, int x_fp32, int B, int G, int C, const
  * dw / db fp32 [C] (optional) = sum dy xhat / sum dy, overwritten. */
 int ivh_batchnorm_cols_bwd(const void* x, int x_fp32, int B, int G, int C, const float* w, const float* mean, const float* rstd, int training,
                            const uint16_t* dy, int64_t ld_dy, const uint16_t* dact, void* dx, int dx_fp32, float* dw, float* db, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Validation and the multi-view test (engines/engine_for_finetuning.py:147-295: validation_one_epoch, final_test, merge, compute_video).
+ * Arguments are checked on the host (< 0, nothing launched), the work goes on `stream`, no float atomics: two runs over the same batches
+ * agree bit for bit.
+ *
+ * The view table of n_videos * n_views slots: `table` (bf16, or fp32 when table_fp32) [slot][ldt] with ldt % 8 == 0, ldt >= V and a 16-byte
+ * aligned base; `owner` int64 [slot], INT64_MAX = empty; `table_label` int32 [slot].  slot = video * n_views + view.
+ * The meter block `meters`: eight 8-byte slots in device memory, zeroed by the caller before the first batch --
+ *   [0] double  sum over the batches of the batch-mean cross entropy      [1] double  sum of fp32(top-1 hits * 100 / M) * M
+ *   [2] double  the same for top-5 (how timm's `accuracy` and MetricLogger.update(acc, n = M) build their totals)
+ *   [3] int64 batches   [4] int64 top-1 hits   [5] int64 top-5 hits   [6] int64 samples   [7] int64 bad rows. */
+/* The row pass of one test batch: logits (bf16, or fp32 when logits_fp32) [M][ld], ld >= V, columns >= V never read; label int32 [M].
+ * loss_rows fp32 [M] = logsumexp - x[label] in fp32; rank_rows int32 [M] = #{c : x_c > x_label} + #{c < label : x_c == x_label} (the tie
+ * rule of ivh_soft_ce_rows); a BAD row stores ~rank (negative): a label outside [0, V) (loss 0, rank V), or, with a table, a video >=
+ * n_videos or a view outside [0, n_views).  meters (optional) += this batch, the losses summed in a fixed order.
+ * View table (video, view, table, owner, table_label: all or none): `the first line read wins` (:267-268) as an atomic 64-bit min of the
+ * sequence number seq_base + row into owner[slot], seq_base = (rank << 40) | rows this rank has added so far; after that claim phase the row
+ * whose number IS the owner stores its logits (zeros in columns V .. ldt-1) and its label.  Two rows of one batch may name one slot; a row
+ * with a larger number than the owner stores nothing.  video < 0: the row updates the meters only.  A bad row is skipped and counted. */
+int ivh_eval_rows(const void* logits, int logits_fp32, int ld, int M, int V, const int32_t* label, const int32_t* video,
+                  const int32_t* view, int64_t seq_base, int n_videos, int n_views, void* table, int table_fp32, int ldt,
+                  int64_t* owner, int32_t* table_label, float* loss_rows, int32_t* rank_rows, int64_t* meters, void* stream);
+/* `merge` / `compute_video` (:246-295) per video: the softmax of every present view (owner != INT64_MAX; an empty slot is never read) in
+ * ascending view order, in fp32, their sum divided by the number of present views; out int32 [n_videos][4] = {count, pred = first maximum of
+ * the mean, rank of the label in the mean (tie rule above), label = the one stored with the lowest present view}; probs (optional) fp32
+ * [n_videos][ldp], ldp >= V: the mean.  A video without a view: {0, -1, -1, -1} and a zero probs row.  V <= 15360. */
+int ivh_view_finalize(const void* table, int table_fp32, int ldt, int V, int n_videos, int n_views, const int64_t* owner,
+                      const int32_t* table_label, int32_t* out, float* probs, int64_t ldp, void* stream);
+/* Multi-rank merge: given `owner` AFTER its all-reduce(MIN) over the ranks, zero every slot (logits row and label) whose owner's rank field
+ * (owner >> 40) is not `rank`, empty slots included.  Every slot then has at most one non-zero contributor, so an all-reduce(SUM) of table
+ * and table_label is exact and every rank holds the table a single process would have built. */
+int ivh_view_mask_owned(void* table, int table_fp32, int ldt, const int64_t* owner, int32_t* table_label, int64_t n_slots, int rank,
+                        void* stream);
 
 #ifdef __cplusplus
 }

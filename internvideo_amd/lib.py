@@ -161,6 +161,9 @@ SIGNATURES = {
     "ivh_cat_pool_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
     "ivh_batchnorm_cols_fwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp],
     "ivh_batchnorm_cols_bwd": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _vp, _i32, _vp, _vp, _vp],
+    "ivh_eval_rows": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp],
+    "ivh_view_finalize": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "ivh_view_mask_owned": [_vp, _i32, _i32, _vp, _vp, _i64, _i32, _vp],
     "ivh_probe_cu_hog": [_vp, _vp, _i64, _i32, _vp],
     "ivh_probe_tr16": [_vp, _vp, _vp],
     "ivh_probe_mfma16": [_vp, _vp, _vp, _vp],

@@ -1218,6 +1218,94 @@ def mixup_target(labels: torch.Tensor, mix: torch.Tensor, smoothing: float, V: i
     return out
 
 
+# ---- validation / multi-view test (evaluate.hip) ------------------------------------------------------------------------------------------
+METER_SLOTS = 8          # loss sum, acc1 total, acc5 total (float64 bits); batches, top-1 hits, top-5 hits, samples, bad rows (int64)
+
+
+def _chk_view_table(what: str, table: torch.Tensor, owner: torch.Tensor, table_label: torch.Tensor):
+    """-> (n_slots, ldt) of a view table: table bf16|fp32 [n_slots, ldt] dense with ldt % 8 == 0, owner int64 [n_slots], labels int32 [n_slots]"""
+    if table.dtype not in (BF16, F32) or not table.is_cuda or table.dim() != 2 or not table.is_contiguous() or table.shape[1] % 8:
+        raise InternVideoHipError(f"{what}: table must be a dense bf16 / fp32 HBM matrix [slots, ldt] with ldt % 8 == 0")
+    n = table.shape[0]
+    _chk_rows(owner, torch.int64, "owner"); _chk_rows(table_label, torch.int32, "table_label")
+    if owner.numel() != n or table_label.numel() != n:
+        raise InternVideoHipError(f"{what}: owner and table_label hold one entry per slot ({n})")
+    return n, table.shape[1]
+
+
+def eval_rows(logits: torch.Tensor, labels: torch.Tensor, V: Optional[int] = None, meters: Optional[torch.Tensor] = None,
+              video: Optional[torch.Tensor] = None, view: Optional[torch.Tensor] = None, seq_base: int = 0, n_views: int = 0,
+              table: Optional[torch.Tensor] = None, owner: Optional[torch.Tensor] = None, table_label: Optional[torch.Tensor] = None):
+    """the row pass of a test batch.  logits bf16|fp32 [M, ld] (columns >= V are padding and never read), labels [M] -> (loss fp32 [M] =
+    logsumexp - x[label], rank int32 [M]; ~rank for a bad row).  meters (int64 [8], see include/internvideo_hip.h) += this batch, in
+    device memory.  With a view table (video / view int [M], table [n_videos * n_views, ldt], owner, table_label): the first row in
+    sequence order (seq_base + row) that names a slot stores its logits and label there; video < 0 updates the meters only."""
+    _L.require_gpu()
+    if not logits.is_cuda:
+        raise InternVideoHipError(f"eval_rows: logits must live in HBM (got device {logits.device}); there is no CPU path")
+    if logits.dtype not in (BF16, F32) or logits.dim() != 2 or logits.stride(1) != 1:
+        raise InternVideoHipError("eval_rows: logits must be a bf16 / fp32 matrix with contiguous rows")
+    M, ld = logits.shape[0], logits.stride(0)
+    V = logits.shape[1] if V is None else int(V)
+    lab = _ids32(labels, "labels")
+    if lab.numel() != M:
+        raise InternVideoHipError("eval_rows: one label per row")
+    if meters is not None:
+        _chk_rows(meters, torch.int64, "meters")
+        if meters.numel() != METER_SLOTS:
+            raise InternVideoHipError(f"eval_rows: the meter block is int64 [{METER_SLOTS}]")
+    vid = vw = None
+    n_videos = ldt = 0
+    if table is not None or video is not None:
+        if table is None or video is None or view is None or owner is None or table_label is None:
+            raise InternVideoHipError("eval_rows: the view table needs video, view, table, owner and table_label together")
+        n_slots, ldt = _chk_view_table("eval_rows", table, owner, table_label)
+        if n_views <= 0 or n_slots % n_views or ldt < V:
+            raise InternVideoHipError(f"eval_rows: {n_slots} slots of pitch {ldt} do not hold n_views = {n_views} views of {V} classes")
+        n_videos = n_slots // n_views
+        vid, vw = _ids32(video, "video"), _ids32(view, "view")
+        if vid.numel() != M or vw.numel() != M:
+            raise InternVideoHipError("eval_rows: one video and one view index per row")
+    dev = logits.device
+    loss = torch.empty((M,), dtype=F32, device=dev)
+    rank = torch.empty((M,), dtype=torch.int32, device=dev)
+    nbytes = M * V * (logits.element_size() * 2 + (table.element_size() if table is not None else 0))
+    _pcall("eval_rows", nbytes, "B", "ivh_eval_rows", ptr(logits), int(logits.dtype == F32), ld, M, V, ptr(lab), ptr(vid), ptr(vw), int(seq_base),
+           n_videos, int(n_views), ptr(table), int(table is not None and table.dtype == F32), ldt, ptr(owner), ptr(table_label), ptr(loss),
+           ptr(rank), ptr(meters), stream_ptr())
+    return loss, rank
+
+
+def view_finalize(table: torch.Tensor, owner: torch.Tensor, table_label: torch.Tensor, n_views: int, V: int, want_probs: bool = False,
+                  out: Optional[torch.Tensor] = None, probs: Optional[torch.Tensor] = None):
+    """softmax of every present view, their mean, argmax and the rank of the label per video -> (int32 [n_videos, 4] = count, pred, rank,
+    label; mean probabilities fp32 [n_videos, V] | None).  out / probs: caller-owned outputs of those shapes."""
+    _L.require_gpu()
+    n_slots, ldt = _chk_view_table("view_finalize", table, owner, table_label)
+    if n_views <= 0 or n_slots % n_views or not 0 < V <= ldt:
+        raise InternVideoHipError(f"view_finalize: {n_slots} slots of pitch {ldt} do not hold n_views = {n_views} views of {V} classes")
+    n_videos = n_slots // n_views
+    if out is None:
+        out = torch.empty((n_videos, 4), dtype=torch.int32, device=table.device)
+    elif _chk_rows(out, torch.int32, "out").shape != (n_videos, 4):
+        raise InternVideoHipError(f"view_finalize: out must be int32 ({n_videos}, 4)")
+    if probs is None and want_probs:
+        probs = torch.empty((n_videos, V), dtype=F32, device=table.device)
+    elif probs is not None and (_chk(probs, F32, "probs").dim() != 2 or probs.shape != (n_videos, V)):
+        raise InternVideoHipError(f"view_finalize: probs must be fp32 ({n_videos}, {V})")
+    _pcall("view_finalize", n_slots * V * table.element_size() * 2, "B", "ivh_view_finalize", ptr(table), int(table.dtype == F32), ldt, int(V),
+           n_videos, int(n_views), ptr(owner), ptr(table_label), ptr(out), ptr(probs), probs.stride(0) if probs is not None else 0, stream_ptr())
+    return out, probs
+
+
+def view_mask_owned(table: torch.Tensor, owner: torch.Tensor, table_label: torch.Tensor, rank: int) -> None:
+    """in place: zero every slot of the table (and its label) whose owner's rank field (owner >> 40) is not `rank`"""
+    _L.require_gpu()
+    n_slots, ldt = _chk_view_table("view_mask_owned", table, owner, table_label)
+    _pcall("view_mask_owned", n_slots * ldt * table.element_size(), "B", "ivh_view_mask_owned", ptr(table), int(table.dtype == F32), ldt, ptr(owner),
+           ptr(table_label), n_slots, int(rank), stream_ptr())
+
+
 # ---- optimizer --------------------------------------------------------------------------------------------------------
 def adamw_step(master, exp_avg, exp_avg_sq, grad, shadow, lr, beta1, beta2, eps, weight_decay, step,
                grad_scale: float = 1.0, clip_coef: Optional[torch.Tensor] = None, lr_segments=None, seg_base: int = 0) -> None:

@@ -14,7 +14,7 @@ implementation: dispatching one on CPU tensors raises the dispatcher's NotImplem
 
 Two groups:
   * building blocks (gemm, gemm_dact, flash_attn_bwd, rmsnorm_add_fwd / _bwd, qk_rmsnorm_bwd, layernorm_fwd, add_layernorm_fwd,
-    cross_entropy_rows, gemm_grouped, adamw_step_ ...): forward / backward kernels as plain operators, no autograd formula;
+    cross_entropy_rows, gemm_grouped, adamw_step_, eval_rows_, view_finalize, view_mask_owned_ ...): forward / backward kernels as plain operators, no autograd formula;
   * the DIFFERENTIABLE fused-op seam of SURVEY.md 8(b) B3 -- `linear`, `fused_mlp`, `rmsnorm_add`, `qk_rmsnorm`, `flash_attn_fwd`,
     `patch_embed_gather`, `decoder_ln_l2_cos_loss`, `contrastive_logits_ce`, `soft_target_cross_entropy` -- each registered with `torch.library.register_autograd`
     (its backward is again a registered operator), checked by `torch.library.opcheck` in tests/test_torch_ops_gpu.py.  The drop-in modules
@@ -590,6 +590,44 @@ for _name, _impl, _meta in (("mix_clips", _mixc, _mixc_meta), ("soft_target_cros
     _LIB.impl(_name, _meta, "Meta")
 torch.library.register_autograd("internvideo_hip::soft_target_cross_entropy", _stce_autograd, setup_context=_stce_setup, lib=_LIB)
 
+# ---- validation / multi-view test: row pass with device-resident meters, view table, finalize, ownership mask (evaluate.hip) ---------------
+_LIB.define("eval_rows_(Tensor logits, Tensor labels, Tensor(a!)? meters=None, Tensor? video=None, Tensor? view=None, int seq_base=0, "
+            "int n_views=0, Tensor(b!)? table=None, Tensor(c!)? owner=None, Tensor(d!)? table_label=None) -> (Tensor, Tensor)")
+_LIB.define("view_finalize(Tensor table, Tensor owner, Tensor table_label, int n_views, int V) -> (Tensor, Tensor)")
+_LIB.define("view_mask_owned_(Tensor(a!) table, Tensor owner, Tensor(b!) table_label, int rank) -> ()")
+
+
+def _evr(logits, labels, meters=None, video=None, view=None, seq_base=0, n_views=0, table=None, owner=None, table_label=None):
+    lg = logits if logits.stride(1) == 1 else logits.contiguous()          # any row pitch >= V passes: unaligned rows are read element-wise
+    return ops.eval_rows(lg, labels, V=logits.shape[1], meters=meters, video=video, view=view, seq_base=seq_base, n_views=n_views, table=table, owner=owner,
+                         table_label=table_label)
+
+
+def _evr_meta(logits, labels, meters=None, video=None, view=None, seq_base=0, n_views=0, table=None, owner=None, table_label=None):
+    return logits.new_empty((logits.shape[0],), dtype=F32), logits.new_empty((logits.shape[0],), dtype=torch.int32)
+
+
+def _vfin(table, owner, table_label, n_views, V):
+    return ops.view_finalize(table, owner, table_label, n_views, V, want_probs=True)
+
+
+def _vfin_meta(table, owner, table_label, n_views, V):
+    n = table.shape[0] // n_views
+    return table.new_empty((n, 4), dtype=torch.int32), table.new_empty((n, V), dtype=F32)
+
+
+def _vmask(table, owner, table_label, rank):
+    ops.view_mask_owned(table, owner, table_label, rank)
+
+
+def _vmask_meta(table, owner, table_label, rank):
+    return None
+
+
+for _name, _impl, _meta in (("eval_rows_", _evr, _evr_meta), ("view_finalize", _vfin, _vfin_meta), ("view_mask_owned_", _vmask, _vmask_meta)):
+    _LIB.impl(_name, _impl, "CUDA")
+    _LIB.impl(_name, _meta, "Meta")
+
 
 DIFFERENTIABLE: Tuple[str, ...] = ("linear", "fused_mlp", "rmsnorm_add", "qk_rmsnorm", "flash_attn_fwd", "patch_embed_gather",
                                    "decoder_ln_l2_cos_loss", "contrastive_logits_ce", "soft_target_cross_entropy")
@@ -597,4 +635,4 @@ OPERATORS: Tuple[str, ...] = ("gemm", "gemm_dact", "flash_attn_fwd", "flash_attn
                               "cross_entropy_rows", "adamw_step_", "rmsnorm_add_bwd", "qk_rmsnorm", "qk_rmsnorm_bwd", "gemm_grouped", "linear",
                               "linear_bwd", "fused_mlp", "fused_mlp_bwd", "rmsnorm_add", "patch_embed_gather", "patch_embed_gather_bwd",
                               "decoder_ln_l2_cos_loss", "decoder_ln_l2_cos_loss_bwd", "contrastive_logits_ce", "mix_clips",
-                              "soft_target_cross_entropy", "soft_target_cross_entropy_bwd")
+                              "soft_target_cross_entropy", "soft_target_cross_entropy_bwd", "eval_rows_", "view_finalize", "view_mask_owned_")
