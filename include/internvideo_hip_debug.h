@@ -43,7 +43,19 @@ int ivh_gemm256_debug_route(const ivh_gemm_desc* d, int mode, int cap, int* out1
  * passed; grid workgroups of 256 threads with shmem_bytes of dynamic LDS.  Returns 0, with ivh_last_error set and out9 untouched, when the
  * entry point would refuse the call. */
 int ivh_rmsnorm_add_debug_route(int bwd, int flavour, unsigned set, int M, int D, int rows_per_sample, int* out9);
-int ivh_gemm256_debug_ablate(int mode);        /* K-loop ablation of the plain NT kernel: 0 off, 1 no MFMA, 2 no LDS-DMA, 3 no fragment reads (garbage results) */
+/* Host logic only (no device needed, nothing dereferenced): the launches one of the six ivh_flash_attn_* entry points would make, chosen by the
+ * route functions the entry points themselves call (flash_attn.hip), under the process's ivh_set_attn_kernel / ivh_probe_attn32_* / stamp-buffer /
+ * IVH_ATTN_* state.  bwd: 0 forward, 1 backward.  dropout != 0: the *_dropout entry (its probability taken as valid).  addr7 = the ADDRESSES
+ * {q, k, v, out, dq, dk, dv}, only tested for NULL and alignment (the forward reads the first four; dout counts as out's address, lse and delta as
+ * present); strides15 = {qsb, qsl, qsh, sb, sl, sh, ob, ol, oh, dqb, dql, dqh, dsb, dsl, dsh}; has_nb_dev != 0: the *_dyn entry with a clip count.
+ * Returns the number of launches (1 forward; 2 backward: dQ, then dK/dV) and 8 ints per launch in out16: {family 16 | 32 (the MFMA shape of the
+ * kernel file), kind, HDP, flags, grid.x, block, dynamic LDS bytes, 0}.  kind: 0 forward (attn_fwd_kernel / attn32_fwd*_kernel), 1 dQ, 2 dK/dV,
+ * 3 the forward as two wave groups (attn32pp_fwd*_kernel).  flags: 1 DROP, 2 DEFER, 4 NP (the *_np_kernel builds), 8 NP2 (attn32_fwd_np2_kernel),
+ * 16 PRIO, 32 GSEL, 64 STAMP (the stamp buffer is handed to the kernel; a template argument of the two-group kernels only).  Returns 0, with
+ * ivh_last_error set and out16 untouched, when the entry point would refuse the call. */
+int ivh_attn_debug_route(int bwd, int dropout, const uint64_t* addr7, const int64_t* strides15, int B, int H, int Lq, int Lk, int hd, int has_nb_dev,
+                         int* out16);
+int ivh_gemm256_debug_ablate(int mode);       /* K-loop ablation of the plain NT kernel: 0 off, 1 no MFMA, 2 no LDS-DMA, 3 no fragment reads (garbage results) */
 
 /* probes used by tests/test_hw_probe.py to pin the hardware semantics the kernels rely on */
 int ivh_probe_tr16(const uint16_t* in_4x16x4, uint16_t* out_64x4, void* stream);

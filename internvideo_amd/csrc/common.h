@@ -171,6 +171,46 @@ inline int launch_row_width(const char* what, int nch, int max_nch, const char* 
   set_error(too_wide, nch * 512);
   return -1;
 }
+
+// ---- attention launches (flash_attn.hip: entry points, routes, the 16x16x32 kernels; flash_attn32.hip: switches, the 32x32x16 kernels) ----
+// Everything the six ivh_flash_attn_* entry points receive.  Pointers a direction does not take are NULL, strides it does not take 0.
+struct AttnArgs {
+  const uint16_t *q, *k, *v;
+  uint16_t* out;                                   // written by the forward, read by the backward
+  const uint16_t* dout;
+  float *lse, *delta;
+  uint16_t *dq, *dk, *dv;
+  int64_t qsb, qsl, qsh, sb, sl, sh, ob, ol, oh, dqb, dql, dqh, dsb, dsl, dsh;   // q; k and v; out and dout; dq; dk and dv
+  int B, H, Lq, Lk, hd;
+  float scale;
+  const int32_t *kv_len, *nb_dev;
+  bool dropout;                                    // a *_dropout entry point (p_drop = 0 is still that entry point)
+  float p_drop;
+  uint32_t seed;
+  const float *qkn_rq, *qkn_rk, *qkn_wqk;          // ivh_probe_attn32_fwd_qkn only
+  void* stream;
+};
+// the arguments every attention entry point shares; the rest of AttnArgs stays NULL / 0
+inline AttnArgs attn_args(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
+                          int64_t ob, int64_t ol, int64_t oh, int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, void* stream) {
+  AttnArgs a{};
+  a.q = q; a.k = k; a.v = v;
+  a.qsb = qsb; a.qsl = qsl; a.qsh = qsh; a.sb = sb; a.sl = sl; a.sh = sh; a.ob = ob; a.ol = ol; a.oh = oh;
+  a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.hd = hd; a.scale = scale; a.kv_len = kv_len; a.stream = stream;
+  return a;
+}
+enum AttnKind { ATTN_FWD = 0, ATTN_DQ = 1, ATTN_DKDV = 2, ATTN_FWD2 = 3 };   // FWD2: the forward as two wave groups (attn32pp_*)
+// template arguments / kernel flavours; STAMP on ATTN_FWD is no template argument: the kernel receives the stamp buffer
+enum AttnFlag { ATTN_DROP = 1, ATTN_DEFER = 2, ATTN_NP = 4, ATTN_NP2 = 8, ATTN_PRIO = 16, ATTN_GSEL = 32, ATTN_STAMP = 64, ATTN_QKN = 128 };
+struct AttnLaunch { int family, kind, hdp, flags; unsigned grid, block, lds; const char* what; };   // family 16 | 32; `what` names it to check_launch
+struct AttnRoute { int n; AttnLaunch launch[2]; };                                                   // backward: dQ, then dK/dV
+inline int attn_hdp(int hd) { return hd <= 64 ? 64 : hd <= 96 ? 96 : 128; }
+// the process-wide measurement switches of the 32x32 kernels, environment defaults (IVH_ATTN_PP, IVH_ATTN_NOPK, IVH_ATTN_DEFER) resolved
+struct Attn32Switches { int pingpong; bool unpacked, defer, stamps; long stamp_rows; };
+Attn32Switches attn32_switches();
+int attn32_supported(const AttnArgs& a);
+int attn32_dkdv_lds_bytes(int Lq, int hd);
+int attn32_launch(const AttnArgs& a, const AttnLaunch& l);
 }  // namespace ivh_host
 
 // ---- internals of the 256x256 GEMM (gemm256.hip) that gemm.hip / gemm_fp8.hip route through; not part of the C ABI headers --------

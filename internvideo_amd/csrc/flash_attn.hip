@@ -468,34 +468,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(HDP <= 64 ?
 }  // namespace ivh
 
 using namespace ivh;
+using namespace ivh_host;
 
-static int attn_check(const void* q, const void* k, const void* v, int64_t qsb, int64_t qsl, int64_t qsh,
-                      int64_t sb, int64_t sl, int64_t sh, int B, int H, int Lq, int Lk, int hd) {
-  IVH_REQUIRE(q && k && v, "flash_attn: null q/k/v");
-  IVH_REQUIRE(B > 0 && H > 0 && Lq > 0 && Lk > 0, "flash_attn: empty problem B=%d H=%d Lq=%d Lk=%d", B, H, Lq, Lk);
-  IVH_REQUIRE(hd > 0 && hd % 8 == 0 && hd <= 128, "flash_attn: head dim %d not supported (multiple of 8, <= 128)", hd);
-  IVH_REQUIRE(sb % 8 == 0 && sl % 8 == 0 && sh % 8 == 0 && qsb % 8 == 0 && qsl % 8 == 0 && qsh % 8 == 0,
-              "flash_attn: strides must be multiples of 8 elements");
-  IVH_REQUIRE(((uintptr_t)q % 16) == 0 && ((uintptr_t)k % 16) == 0 && ((uintptr_t)v % 16) == 0, "flash_attn: q/k/v must be 16-byte aligned");
-  IVH_REQUIRE(H <= 65535 && B <= 65535, "flash_attn: B, H must be <= 65535");
-  return 0;
-}
-
-// 32x32x16-MFMA kernels (flash_attn32.hip)
-extern "C" int ivh_attn32_supported(int64_t qsb, int64_t qsl, int64_t qsh, int64_t sb, int64_t sl, int64_t sh,
-                                    int64_t ob, int64_t ol, int64_t oh, int Lq, int Lk, int hd);
-extern "C" int ivh_attn32_fwd_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                     uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse, int B, int H, int Lq, int Lk, int hd, float scale,
-                                     const int32_t* kv_len, const int32_t* nb_dev, void* stream);
-extern "C" int ivh_attn32_bwd_dq_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                        const uint16_t* out, const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh, const float* lse, float* delta,
-                                        uint16_t* dq, int64_t dqb, int64_t dql, int64_t dqh, int B, int H, int Lq, int Lk, int hd, float scale,
-                                        const int32_t* kv_len, const int32_t* nb_dev, void* stream);
-extern "C" int ivh_attn32_dkdv_lds_bytes(int Lq, int hd);
-extern "C" int ivh_attn32_bwd_dkdv_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                          const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh, const float* lse, const float* delta,
-                                          uint16_t* dk, uint16_t* dv, int64_t dsb, int64_t dsl, int64_t dsh, int B, int H, int Lq, int Lk, int hd, float scale,
-                                          const int32_t* kv_len, const int32_t* nb_dev, void* stream);
 // 0 = automatic (the 32x32 kernels whenever they support the problem), 1 = the 16x16x32 kernels of this file, 2 = 32x32 or error
 static int g_attn_impl = 0;
 extern "C" int ivh_set_attn_kernel(int choice) {
@@ -504,35 +478,15 @@ extern "C" int ivh_set_attn_kernel(int choice) {
   return 0;
 }
 
-#define IVH_ATTN_DISPATCH(hd, KERNEL, grid, s, ...)                                                     \
-  if ((hd) <= 64) hipLaunchKernelGGL((KERNEL<64>), grid, dim3(256), 0, s, __VA_ARGS__);                 \
-  else if ((hd) <= 96) hipLaunchKernelGGL((KERNEL<96>), grid, dim3(256), 0, s, __VA_ARGS__);            \
-  else hipLaunchKernelGGL((KERNEL<128>), grid, dim3(256), 0, s, __VA_ARGS__);
-
-// nb_dev (ivh_flash_attn_fwd_dyn / _bwd_dyn, ABI 2): int32 in HBM, the number of clips that exist -- the launch is sized for B, workgroups of
-// clips at or past *nb_dev leave at once and none of their outputs is written (DropPath skipping: the kept clips of a branch are compacted
-// to the front).  32x32 kernels only.
-extern "C" int ivh_flash_attn_fwd_dyn(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                      const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                      uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse,
-                                      int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, const int32_t* nb_dev, void* stream) {
-  if (attn_check(q, k, v, qsb, qsl, qsh, sb, sl, sh, B, H, Lq, Lk, hd)) return -1;
-  IVH_REQUIRE(out && ((uintptr_t)out % 8) == 0 && ob % 4 == 0 && ol % 4 == 0 && oh % 4 == 0, "flash_attn_fwd: bad out");
-  const bool ok32 = ((uintptr_t)out % 16) == 0 && ivh_attn32_supported(qsb, qsl, qsh, sb, sl, sh, ob, ol, oh, Lq, Lk, hd);
-  IVH_REQUIRE(g_attn_impl != 2 || ok32, "flash_attn_fwd: the 32x32 kernel was requested but does not support these strides / sizes");
-  IVH_REQUIRE(!nb_dev || (ok32 && g_attn_impl != 1), "flash_attn_fwd_dyn: a device-side clip count needs the 32x32 kernels, which do not support this layout");
-  if (g_attn_impl != 1 && ok32)
-    return ivh_attn32_fwd_launch(q, qsb, qsl, qsh, k, v, sb, sl, sh, out, ob, ol, oh, lse, B, H, Lq, Lk, hd, scale, kv_len, nb_dev, stream);
-  dim3 grid((unsigned)((long)((Lq + 64 * ivh::ATTN_FWD_QW - 1) / (64 * ivh::ATTN_FWD_QW)) * H * B), 1, 1);
-  IVH_ATTN_DISPATCH(hd, attn_fwd_kernel, grid, (hipStream_t)stream, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh,
-                    out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len);
-  return ivh_host::check_launch("flash_attn_fwd");
-}
-extern "C" int ivh_flash_attn_fwd(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                  const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                  uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse,
-                                  int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, void* stream) {
-  return ivh_flash_attn_fwd_dyn(q, qsb, qsl, qsh, k, v, sb, sl, sh, out, ob, ol, oh, lse, B, H, Lq, Lk, hd, scale, kv_len, nullptr, stream);
+static int attn_check(const AttnArgs& a) {
+  IVH_REQUIRE(a.q && a.k && a.v, "flash_attn: null q/k/v");
+  IVH_REQUIRE(a.B > 0 && a.H > 0 && a.Lq > 0 && a.Lk > 0, "flash_attn: empty problem B=%d H=%d Lq=%d Lk=%d", a.B, a.H, a.Lq, a.Lk);
+  IVH_REQUIRE(a.hd > 0 && a.hd % 8 == 0 && a.hd <= 128, "flash_attn: head dim %d not supported (multiple of 8, <= 128)", a.hd);
+  IVH_REQUIRE(a.sb % 8 == 0 && a.sl % 8 == 0 && a.sh % 8 == 0 && a.qsb % 8 == 0 && a.qsl % 8 == 0 && a.qsh % 8 == 0,
+              "flash_attn: strides must be multiples of 8 elements");
+  IVH_REQUIRE(((uintptr_t)a.q % 16) == 0 && ((uintptr_t)a.k % 16) == 0 && ((uintptr_t)a.v % 16) == 0, "flash_attn: q/k/v must be 16-byte aligned");
+  IVH_REQUIRE(a.H <= 65535 && a.B <= 65535, "flash_attn: B, H must be <= 65535");
+  return 0;
 }
 
 static int drop_cfg(float p, uint32_t seed, DropCfg* d) {
@@ -545,84 +499,213 @@ static int drop_cfg(float p, uint32_t seed, DropCfg* d) {
   return 0;
 }
 
-// Attention with dropout on the probabilities (the 16x16x32 kernels of this file, head dims <= 64: the text tower's).  Same arguments as
-// ivh_flash_attn_fwd / _bwd plus the drop probability and the seed of the counter-based mask; the same (p, seed) must be given to both.
-extern "C" int ivh_flash_attn_fwd_dropout(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                          const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                          uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse,
-                                          int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len,
-                                          float p_drop, uint32_t seed, void* stream) {
-  if (attn_check(q, k, v, qsb, qsl, qsh, sb, sl, sh, B, H, Lq, Lk, hd)) return -1;
-  IVH_REQUIRE(out && ((uintptr_t)out % 8) == 0 && ob % 4 == 0 && ol % 4 == 0 && oh % 4 == 0, "flash_attn_fwd_dropout: bad out");
-  IVH_REQUIRE(hd <= 64, "flash_attn_fwd_dropout: built for head dims <= 64 (got %d)", hd);
-  DropCfg d;
-  if (drop_cfg(p_drop, seed, &d)) return -1;
-  dim3 grid((unsigned)((long)((Lq + 64 * ivh::ATTN_FWD_QW - 1) / (64 * ivh::ATTN_FWD_QW)) * H * B), 1, 1);
-  hipLaunchKernelGGL((attn_fwd_kernel<64, true>), grid, dim3(256), 0, (hipStream_t)stream, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                     (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, d);
-  return ivh_host::check_launch("flash_attn_fwd_dropout");
+// one workgroup per `rows` rows of a (b, h) slice
+static long attn_wgs(const AttnArgs& a, int L, int rows) { return (long)((L + rows - 1) / rows) * a.H * a.B; }
+
+// ---- routes: which kernel(s) a call runs, on what grid.  They launch nothing and dereference nothing; the entry points and ivh_attn_debug_route
+// call these two and nothing else decides.
+// Dropout on the probabilities (the *_dropout entry points) exists on the 16x16x32 kernels at head dims <= 64 only: the text tower's.
+// nb_dev (the *_dyn entry points, ABI 2): int32 in HBM, the number of clips that exist -- the launch is sized for B, workgroups of clips at or past
+// *nb_dev leave at once and none of their outputs is written (DropPath skipping: the kept clips of a branch are compacted to the front).  Needs
+// the 32x32 forward / dQ kernel; either dK/dV kernel takes it.
+static int route_attn_fwd(const AttnArgs& a, AttnRoute* r) {
+  const char* name = a.dropout ? "flash_attn_fwd_dropout" : "flash_attn_fwd";
+  if (attn_check(a)) return -1;
+  IVH_REQUIRE(a.out && ((uintptr_t)a.out % 8) == 0 && a.ob % 4 == 0 && a.ol % 4 == 0 && a.oh % 4 == 0, "%s: bad out", name);
+  const int hdp = attn_hdp(a.hd);
+  const bool mid = hdp == 96;                             // the measurement variants below are built for 64 < hd <= 96 only
+  AttnLaunch& l = r->launch[0];
+  r->n = 1;
+  l = AttnLaunch{16, ATTN_FWD, hdp, 0, (unsigned)attn_wgs(a, a.Lq, 64 * ATTN_FWD_QW), 256, 0, name};
+  if (a.dropout) {
+    DropCfg d;
+    IVH_REQUIRE(a.hd <= 64, "flash_attn_fwd_dropout: built for head dims <= 64 (got %d)", a.hd);
+    l.flags = ATTN_DROP;
+    return drop_cfg(a.p_drop, a.seed, &d);
+  }
+  const bool ok32 = ((uintptr_t)a.out % 16) == 0 && attn32_supported(a);
+  IVH_REQUIRE(g_attn_impl != 2 || ok32, "flash_attn_fwd: the 32x32 kernel was requested but does not support these strides / sizes");
+  IVH_REQUIRE(!a.nb_dev || (ok32 && g_attn_impl != 1), "flash_attn_fwd_dyn: a device-side clip count needs the 32x32 kernels, which do not support this layout");
+  if (g_attn_impl == 1 || !ok32) return 0;
+  const Attn32Switches sw = attn32_switches();
+  const int pp = sw.pingpong;
+  if (pp >= 1 && pp <= 5 && (mid || !sw.stamps)) {        // two wave groups one phase apart; with a stamp buffer only where the stamping build exists
+    l = AttnLaunch{32, ATTN_FWD2, hdp, 0, (unsigned)attn_wgs(a, a.Lq, 256), 512, 0, "flash_attn_fwd (32x32, two wave groups)"};
+    if (sw.stamps) {                                      // segment stamps of workgroup 0, waves 0 and 4: [2][256] (tools/probes/attn_pp_stamps.py)
+      IVH_REQUIRE(sw.stamp_rows >= 128, "flash_attn_fwd: the two-group stamp buffer holds 2 x 256 uint64");
+      l.flags = ATTN_STAMP | (pp >= 4 ? ATTN_NP : 0);
+      l.what = "flash_attn_fwd (32x32, two wave groups, stamps)";
+    } else if (mid && pp >= 4) {                          // unpacked softmax arithmetic (5: + raised priority)
+      l.flags = ATTN_NP | (pp == 5 ? ATTN_PRIO : 0);
+      l.what = "flash_attn_fwd (32x32, two wave groups, unpacked softmax)";
+    } else if (mid && pp == 3) {                          // groups = even / odd waves
+      l.flags = ATTN_GSEL;
+      l.what = "flash_attn_fwd (32x32, two wave groups, alternating)";
+    } else {                                              // 1: plain, 2: MFMA segments at raised priority; 3 / 4 / 5 outside (64, 96] are 1
+      l.flags = pp == 2 ? ATTN_PRIO : 0;
+    }
+    return 0;
+  }
+  const long wgs = attn_wgs(a, a.Lq, 128);
+  l = AttnLaunch{32, ATTN_FWD, hdp, 0, (unsigned)wgs, 256, 0, "flash_attn_fwd (32x32)"};
+  if (pp == 7 && mid && !sw.stamps) {                     // the shipped kernel at two waves per SIMD
+    l.flags = ATTN_NP2;
+    l.what = "flash_attn_fwd (32x32, two waves per SIMD)";
+  } else if (pp == 6 && mid && !sw.stamps) {              // the one-group kernel with unpacked softmax arithmetic, whatever IVH_ATTN_NOPK says
+    l.flags = ATTN_NP;
+    l.what = "flash_attn_fwd (32x32, unpacked softmax)";
+  } else {                                                // the shipped route: unpacked unless switched off; IVH_ATTN_DEFER=1 is packed outside (64, 96]
+    if (sw.defer && sw.unpacked && mid) l.what = "flash_attn_fwd (32x32, deferred rescale)";
+    l.flags = sw.defer ? (ATTN_DEFER | (sw.unpacked && mid ? ATTN_NP : 0)) : (sw.unpacked ? ATTN_NP : 0);
+    if (sw.stamps) {                                      // this kernel writes 4 stamps per workgroup of the WHOLE grid, under every ping-pong mode
+      IVH_REQUIRE(wgs <= sw.stamp_rows, "flash_attn_fwd: the stamp buffer holds %ld workgroups", sw.stamp_rows);
+      l.flags |= ATTN_STAMP;
+    }
+  }
+  return 0;
 }
 
-extern "C" int ivh_flash_attn_bwd_dropout(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                          const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                          const uint16_t* out, const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh,
-                                          const float* lse, float* delta, uint16_t* dq, int64_t dqb, int64_t dql, int64_t dqh,
-                                          uint16_t* dk, uint16_t* dv, int64_t dsb, int64_t dsl, int64_t dsh,
-                                          int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len,
-                                          float p_drop, uint32_t seed, void* stream) {
-  if (attn_check(q, k, v, qsb, qsl, qsh, sb, sl, sh, B, H, Lq, Lk, hd)) return -1;
-  IVH_REQUIRE(out && dout && lse && delta && dq && dk && dv, "flash_attn_bwd_dropout: null argument");
-  IVH_REQUIRE(ob % 8 == 0 && ol % 8 == 0 && oh % 8 == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)dout % 16) == 0, "flash_attn_bwd_dropout: out/dout alignment");
-  IVH_REQUIRE(dsb % 4 == 0 && dsl % 4 == 0 && dsh % 4 == 0 && dqb % 4 == 0 && dql % 4 == 0 && dqh % 4 == 0, "flash_attn_bwd_dropout: dq/dk/dv strides must be multiples of 4");
-  IVH_REQUIRE(hd <= 64, "flash_attn_bwd_dropout: built for head dims <= 64 (got %d)", hd);
-  DropCfg d;
-  if (drop_cfg(p_drop, seed, &d)) return -1;
-  hipStream_t s = (hipStream_t)stream;
-  dim3 gk((unsigned)((long)((Lk + 63) / 64) * H * B), 1, 1), gq((unsigned)((long)((Lq + 63) / 64) * H * B), 1, 1);
-  hipLaunchKernelGGL((attn_bwd_dq_kernel<64, true>), gq, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, out, dout,
-                     (long)ob, (long)ol, (long)oh, lse, delta, dq, (long)dqb, (long)dql, (long)dqh, H, Lq, Lk, hd, scale, kv_len, d);
-  hipLaunchKernelGGL((attn_bwd_dkdv_kernel<64, true>), gk, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, dout,
-                     (long)ob, (long)ol, (long)oh, lse, delta, dk, dv, (long)dsb, (long)dsl, (long)dsh, H, Lq, Lk, hd, scale, kv_len, d);
-  return ivh_host::check_launch("flash_attn_bwd_dropout");
-}
-
-extern "C" int ivh_flash_attn_bwd_dyn(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                      const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                      const uint16_t* out, const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh,
-                                      const float* lse, float* delta, uint16_t* dq, int64_t dqb, int64_t dql, int64_t dqh,
-                                      uint16_t* dk, uint16_t* dv, int64_t dsb, int64_t dsl, int64_t dsh,
-                                      int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, const int32_t* nb_dev, void* stream) {
-  if (attn_check(q, k, v, qsb, qsl, qsh, sb, sl, sh, B, H, Lq, Lk, hd)) return -1;
-  IVH_REQUIRE(out && dout && lse && delta && dq && dk && dv, "flash_attn_bwd: null argument");
-  IVH_REQUIRE(ob % 8 == 0 && ol % 8 == 0 && oh % 8 == 0 && ((uintptr_t)out % 16) == 0 && ((uintptr_t)dout % 16) == 0, "flash_attn_bwd: out/dout alignment");
-  IVH_REQUIRE(dsb % 4 == 0 && dsl % 4 == 0 && dsh % 4 == 0 && dqb % 4 == 0 && dql % 4 == 0 && dqh % 4 == 0, "flash_attn_bwd: dq/dk/dv strides must be multiples of 4");
-  hipStream_t s = (hipStream_t)stream;
-  dim3 gk((unsigned)((long)((Lk + 63) / 64) * H * B), 1, 1), gq((unsigned)((long)((Lq + 63) / 64) * H * B), 1, 1);
-  const bool al16 = ((uintptr_t)dq % 16) == 0 && ((uintptr_t)dk % 16) == 0 && ((uintptr_t)dv % 16) == 0 && dqb % 8 == 0 && dql % 8 == 0 && dqh % 8 == 0 &&
-                    dsb % 8 == 0 && dsl % 8 == 0 && dsh % 8 == 0;
-  const bool ok32 = al16 && ivh_attn32_supported(qsb, qsl, qsh, sb, sl, sh, ob, ol, oh, Lq, Lk, hd);
+// dQ first: its prologue computes delta = <dO, O> per query row and leaves it in `delta` for the dK/dV kernel that follows
+static int route_attn_bwd(const AttnArgs& a, AttnRoute* r) {
+  const char* name = a.dropout ? "flash_attn_bwd_dropout" : "flash_attn_bwd";
+  if (attn_check(a)) return -1;
+  IVH_REQUIRE(a.out && a.dout && a.lse && a.delta && a.dq && a.dk && a.dv, "%s: null argument", name);
+  IVH_REQUIRE(a.ob % 8 == 0 && a.ol % 8 == 0 && a.oh % 8 == 0 && ((uintptr_t)a.out % 16) == 0 && ((uintptr_t)a.dout % 16) == 0, "%s: out/dout alignment", name);
+  IVH_REQUIRE(a.dsb % 4 == 0 && a.dsl % 4 == 0 && a.dsh % 4 == 0 && a.dqb % 4 == 0 && a.dql % 4 == 0 && a.dqh % 4 == 0, "%s: dq/dk/dv strides must be multiples of 4", name);
+  const int hdp = attn_hdp(a.hd);
+  AttnLaunch &dq = r->launch[0], &dkdv = r->launch[1];
+  r->n = 2;
+  dq = AttnLaunch{16, ATTN_DQ, hdp, 0, (unsigned)attn_wgs(a, a.Lq, 64), 256, 0, name};
+  dkdv = AttnLaunch{16, ATTN_DKDV, hdp, 0, (unsigned)attn_wgs(a, a.Lk, 64), 256, 0, name};
+  if (a.dropout) {
+    DropCfg d;
+    IVH_REQUIRE(a.hd <= 64, "flash_attn_bwd_dropout: built for head dims <= 64 (got %d)", a.hd);
+    dq.flags = dkdv.flags = ATTN_DROP;
+    return drop_cfg(a.p_drop, a.seed, &d);
+  }
+  const bool al16 = ((uintptr_t)a.dq % 16) == 0 && ((uintptr_t)a.dk % 16) == 0 && ((uintptr_t)a.dv % 16) == 0 && a.dqb % 8 == 0 && a.dql % 8 == 0 && a.dqh % 8 == 0 &&
+                    a.dsb % 8 == 0 && a.dsl % 8 == 0 && a.dsh % 8 == 0;
+  const bool ok32 = al16 && attn32_supported(a);
   IVH_REQUIRE(g_attn_impl != 2 || ok32, "flash_attn_bwd: the 32x32 kernels were requested but do not support these strides / sizes");
   const bool use32 = g_attn_impl != 1 && ok32;
-  IVH_REQUIRE(!nb_dev || use32, "flash_attn_bwd_dyn: a device-side clip count needs the 32x32 dQ kernel, which does not support this layout");
-  // dQ first: its prologue computes delta = <dO, O> per query row and leaves it in `delta` for the dK/dV kernel that follows
-  if (use32) {
-    if (ivh_attn32_bwd_dq_launch(q, qsb, qsl, qsh, k, v, sb, sl, sh, out, dout, ob, ol, oh, lse, delta, dq, dqb, dql, dqh, B, H, Lq, Lk, hd, scale, kv_len, nb_dev, stream)) return -1;
-  } else {
-    IVH_ATTN_DISPATCH(hd, attn_bwd_dq_kernel, gq, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, out, dout, (long)ob, (long)ol, (long)oh,
-                      lse, delta, dq, (long)dqb, (long)dql, (long)dqh, H, Lq, Lk, hd, scale, kv_len);
-  }
-  if (use32 && ivh_attn32_dkdv_lds_bytes(Lq, hd) > 0)       // head dims above 96 stay on the 16x16 dK/dV kernel (the 32x32 one would spill)
-    return ivh_attn32_bwd_dkdv_launch(q, qsb, qsl, qsh, k, v, sb, sl, sh, dout, ob, ol, oh, lse, delta, dk, dv, dsb, dsl, dsh, B, H, Lq, Lk, hd, scale, kv_len, nb_dev, stream);
-  IVH_ATTN_DISPATCH(hd, attn_bwd_dkdv_kernel, gk, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, dout, (long)ob, (long)ol, (long)oh,
-                    lse, delta, dk, dv, (long)dsb, (long)dsl, (long)dsh, H, Lq, Lk, hd, scale, kv_len, DropCfg{0u, 1.0f, 0u}, nb_dev);
-  return ivh_host::check_launch("flash_attn_bwd");
+  IVH_REQUIRE(!a.nb_dev || use32, "flash_attn_bwd_dyn: a device-side clip count needs the 32x32 dQ kernel, which does not support this layout");
+  if (!use32) return 0;
+  const int np = attn32_switches().unpacked ? ATTN_NP : 0;
+  dq = AttnLaunch{32, ATTN_DQ, hdp, np, (unsigned)attn_wgs(a, a.Lq, 128), 256, 0, "flash_attn_bwd dq (32x32)"};
+  const int lds = attn32_dkdv_lds_bytes(a.Lq, a.hd);      // 0: head dims above 96 (the 32x32 kernel would spill) and very long Lq stay on the 16x16 dK/dV kernel
+  if (lds > 0) dkdv = AttnLaunch{32, ATTN_DKDV, hdp, np, (unsigned)attn_wgs(a, a.Lk, 128), 256, (unsigned)lds, "flash_attn_bwd dkdv (32x32)"};
+  return 0;
 }
-extern "C" int ivh_flash_attn_bwd(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                  const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                  const uint16_t* out, const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh,
-                                  const float* lse, float* delta, uint16_t* dq, int64_t dqb, int64_t dql, int64_t dqh,
-                                  uint16_t* dk, uint16_t* dv, int64_t dsb, int64_t dsl, int64_t dsh,
-                                  int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, void* stream) {
-  return ivh_flash_attn_bwd_dyn(q, qsb, qsl, qsh, k, v, sb, sl, sh, out, dout, ob, ol, oh, lse, delta, dq, dqb, dql, dqh, dk, dv, dsb, dsl, dsh,
-                                B, H, Lq, Lk, hd, scale, kv_len, nullptr, stream);
+
+// ---- launches.  Every 16x16x32 instantiation that exists, once: taking the address instantiates the kernel, and a launch whose key has no row
+// is an error, never another flavour.  The 32x32 table is attn32_launch's (flash_attn32.hip).
+struct Attn16Row { int kind, hdp, flags; void* fn; };
+#define A16_ROWS(hdp, drop)                                                                                                                  \
+  {ATTN_FWD, hdp, (drop) ? ATTN_DROP : 0, (void*)&attn_fwd_kernel<hdp, drop>}, {ATTN_DQ, hdp, (drop) ? ATTN_DROP : 0, (void*)&attn_bwd_dq_kernel<hdp, drop>}, \
+      {ATTN_DKDV, hdp, (drop) ? ATTN_DROP : 0, (void*)&attn_bwd_dkdv_kernel<hdp, drop>}
+static const Attn16Row attn16_table[] = {A16_ROWS(64, false), A16_ROWS(96, false), A16_ROWS(128, false), A16_ROWS(64, true)};
+#undef A16_ROWS
+
+static int attn_launch(const AttnArgs& a, const AttnLaunch& l) {
+  if (l.family == 32) return attn32_launch(a, l);
+  void* fn = nullptr;
+  for (const Attn16Row& row : attn16_table)
+    if (row.kind == l.kind && row.hdp == l.hdp && row.flags == l.flags) fn = row.fn;
+  IVH_REQUIRE(fn, "%s: the 16x16 attention kernel of kind %d, HDP %d, flags 0x%x is not built", l.what, l.kind, l.hdp, l.flags);
+  DropCfg d{0u, 1.0f, 0u};
+  if (a.dropout && drop_cfg(a.p_drop, a.seed, &d)) return -1;
+  const dim3 grid(l.grid, 1, 1), block(l.block);
+  hipStream_t s = (hipStream_t)a.stream;
+  switch (l.kind) {
+    case ATTN_FWD:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn_fwd_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.out, a.ob, a.ol, a.oh, a.lse, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, d);
+      break;
+    case ATTN_DQ:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn_bwd_dq_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.out, a.dout, a.ob, a.ol, a.oh, a.lse, a.delta, a.dq, a.dqb, a.dql, a.dqh, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, d);
+      break;
+    default:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn_bwd_dkdv_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.dout, a.ob, a.ol, a.oh, a.lse, a.delta, a.dk, a.dv, a.dsb, a.dsl, a.dsh, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, d, a.nb_dev);
+  }
+  return check_launch(l.what);
+}
+
+static int attn_fwd(const AttnArgs& a) {
+  AttnRoute r;
+  return route_attn_fwd(a, &r) ? -1 : attn_launch(a, r.launch[0]);
+}
+static int attn_bwd(const AttnArgs& a) {
+  AttnRoute r;
+  if (route_attn_bwd(a, &r) || attn_launch(a, r.launch[0])) return -1;
+  return attn_launch(a, r.launch[1]);
+}
+
+// ---- the C ABI (include/internvideo_hip.h, which this file includes: a list that drifts from the declaration does not compile).  The three
+// flavours of a direction share its parameters up to kv_len; each is a thin wrapper that fills AttnArgs.
+#define ATTN_FWD_PARAMS                                                                                                                   \
+  const uint16_t *q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t *k, const uint16_t *v, int64_t sb, int64_t sl, int64_t sh, uint16_t *out, \
+      int64_t ob, int64_t ol, int64_t oh, float *lse, int B, int H, int Lq, int Lk, int hd, float scale, const int32_t *kv_len
+#define ATTN_FWD_NAMES q, qsb, qsl, qsh, k, v, sb, sl, sh, out, ob, ol, oh, lse, B, H, Lq, Lk, hd, scale, kv_len
+#define ATTN_BWD_PARAMS                                                                                                                   \
+  const uint16_t *q, int64_t qsb, int64_t qsl, int64_t qsh, const uint16_t *k, const uint16_t *v, int64_t sb, int64_t sl, int64_t sh, const uint16_t *out, \
+      const uint16_t *dout, int64_t ob, int64_t ol, int64_t oh, const float *lse, float *delta, uint16_t *dq, int64_t dqb, int64_t dql, int64_t dqh,      \
+      uint16_t *dk, uint16_t *dv, int64_t dsb, int64_t dsl, int64_t dsh, int B, int H, int Lq, int Lk, int hd, float scale, const int32_t *kv_len
+#define ATTN_BWD_NAMES q, qsb, qsl, qsh, k, v, sb, sl, sh, out, dout, ob, ol, oh, lse, delta, dq, dqb, dql, dqh, dk, dv, dsb, dsl, dsh, B, H, Lq, Lk, hd, scale, kv_len
+static AttnArgs attn_fwd_args(ATTN_FWD_PARAMS, void* stream) {
+  AttnArgs a = attn_args(q, qsb, qsl, qsh, k, v, sb, sl, sh, ob, ol, oh, B, H, Lq, Lk, hd, scale, kv_len, stream);
+  a.out = out; a.lse = lse;
+  return a;
+}
+static AttnArgs attn_bwd_args(ATTN_BWD_PARAMS, void* stream) {
+  AttnArgs a = attn_args(q, qsb, qsl, qsh, k, v, sb, sl, sh, ob, ol, oh, B, H, Lq, Lk, hd, scale, kv_len, stream);
+  a.out = const_cast<uint16_t*>(out); a.dout = dout; a.lse = const_cast<float*>(lse); a.delta = delta;
+  a.dq = dq; a.dqb = dqb; a.dql = dql; a.dqh = dqh; a.dk = dk; a.dv = dv; a.dsb = dsb; a.dsl = dsl; a.dsh = dsh;
+  return a;
+}
+static int attn_run(AttnArgs a, bool bwd, const int32_t* nb_dev, bool dropout, float p_drop, uint32_t seed) {
+  a.nb_dev = nb_dev; a.dropout = dropout; a.p_drop = p_drop; a.seed = seed;
+  return bwd ? attn_bwd(a) : attn_fwd(a);
+}
+extern "C" int ivh_flash_attn_fwd(ATTN_FWD_PARAMS, void* stream) { return attn_run(attn_fwd_args(ATTN_FWD_NAMES, stream), false, nullptr, false, 0.0f, 0u); }
+extern "C" int ivh_flash_attn_bwd(ATTN_BWD_PARAMS, void* stream) { return attn_run(attn_bwd_args(ATTN_BWD_NAMES, stream), true, nullptr, false, 0.0f, 0u); }
+extern "C" int ivh_flash_attn_fwd_dyn(ATTN_FWD_PARAMS, const int32_t* nb_dev, void* stream) {
+  return attn_run(attn_fwd_args(ATTN_FWD_NAMES, stream), false, nb_dev, false, 0.0f, 0u);
+}
+extern "C" int ivh_flash_attn_bwd_dyn(ATTN_BWD_PARAMS, const int32_t* nb_dev, void* stream) {
+  return attn_run(attn_bwd_args(ATTN_BWD_NAMES, stream), true, nb_dev, false, 0.0f, 0u);
+}
+// dropout on the probabilities: the drop probability and the seed of the counter-based mask; the same (p, seed) must be given to both directions
+extern "C" int ivh_flash_attn_fwd_dropout(ATTN_FWD_PARAMS, float p_drop, uint32_t seed, void* stream) {
+  return attn_run(attn_fwd_args(ATTN_FWD_NAMES, stream), false, nullptr, true, p_drop, seed);
+}
+extern "C" int ivh_flash_attn_bwd_dropout(ATTN_BWD_PARAMS, float p_drop, uint32_t seed, void* stream) {
+  return attn_run(attn_bwd_args(ATTN_BWD_NAMES, stream), true, nullptr, true, p_drop, seed);
+}
+#undef ATTN_BWD_NAMES
+#undef ATTN_BWD_PARAMS
+#undef ATTN_FWD_NAMES
+#undef ATTN_FWD_PARAMS
+
+// ---- ivh_attn_debug_route (include/internvideo_hip_debug.h): the routes above, seen from outside.  Host logic only.
+extern "C" int ivh_attn_debug_route(int bwd, int dropout, const uint64_t* addr7, const int64_t* strides15, int B, int H, int Lq, int Lk, int hd,
+                                    int has_nb_dev, int* out16) {
+  static float present_f;                                 // stands for the pointers the route only tests for NULL
+  static int32_t present_i;
+  const int64_t* st = strides15;
+  const auto at = [&](int i) { return reinterpret_cast<uint16_t*>((uintptr_t)addr7[i]); };
+  AttnArgs a = bwd ? attn_bwd_args(at(0), st[0], st[1], st[2], at(1), at(2), st[3], st[4], st[5], at(3), at(3), st[6], st[7], st[8], &present_f, &present_f, at(4), st[9],
+                                   st[10], st[11], at(5), at(6), st[12], st[13], st[14], B, H, Lq, Lk, hd, 1.0f, nullptr, nullptr)
+                   : attn_fwd_args(at(0), st[0], st[1], st[2], at(1), at(2), st[3], st[4], st[5], at(3), st[6], st[7], st[8], &present_f, B, H, Lq, Lk, hd, 1.0f, nullptr, nullptr);
+  a.nb_dev = has_nb_dev ? &present_i : nullptr;
+  a.dropout = dropout != 0;
+  AttnRoute r;
+  if (bwd ? route_attn_bwd(a, &r) : route_attn_fwd(a, &r)) return 0;
+  for (int i = 0; i < r.n; ++i) {
+    const AttnLaunch& l = r.launch[i];
+    const int row[8] = {l.family, l.kind, l.hdp, l.flags, (int)l.grid, (int)l.block, (int)l.lds, 0};
+    for (int j = 0; j < 8; ++j) out16[8 * i + j] = row[j];
+  }
+  return r.n;
 }

@@ -936,25 +936,28 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2), target(
 }  // namespace ivh
 
 using namespace ivh;
+using namespace ivh_host;
 
 // Can the 32x32 kernels take this problem?  16-byte stores / DMA chunks: every stride a multiple of 8 elements, every (b, h)
 // slice addressable with 31-bit byte offsets.
-extern "C" int ivh_attn32_supported(int64_t qsb, int64_t qsl, int64_t qsh, int64_t sb, int64_t sl, int64_t sh,
-                                    int64_t ob, int64_t ol, int64_t oh, int Lq, int Lk, int hd) {
-  (void)qsb; (void)sb; (void)ob;
-  if (hd % 8 || hd > 128 || hd <= 0) return 0;
-  if ((qsl % 8) || (qsh % 8) || (sl % 8) || (sh % 8) || (ol % 8) || (oh % 8) || (qsb % 8) || (sb % 8) || (ob % 8)) return 0;
+int ivh_host::attn32_supported(const AttnArgs& a) {
+  if (a.hd % 8 || a.hd > 128 || a.hd <= 0) return 0;
+  if ((a.qsl % 8) || (a.qsh % 8) || (a.sl % 8) || (a.sh % 8) || (a.ol % 8) || (a.oh % 8) || (a.qsb % 8) || (a.sb % 8) || (a.ob % 8)) return 0;
   const int64_t lim = (1LL << 31) - (1 << 20);
-  if (((int64_t)Lk + 64) * sl * 2 >= lim || ((int64_t)Lq + 64) * qsl * 2 >= lim || ((int64_t)Lq + 64) * ol * 2 >= lim) return 0;
+  if (((int64_t)a.Lk + 64) * a.sl * 2 >= lim || ((int64_t)a.Lq + 64) * a.qsl * 2 >= lim || ((int64_t)a.Lq + 64) * a.ol * 2 >= lim) return 0;
   return 1;
 }
 
-#define IVH_ATTN32_DISPATCH(hd, KERNEL, grid, s, ...)                                                   \
-  if ((hd) <= 64) hipLaunchKernelGGL((KERNEL<64>), grid, dim3(256), 0, s, __VA_ARGS__);                 \
-  else if ((hd) <= 96) hipLaunchKernelGGL((KERNEL<96>), grid, dim3(256), 0, s, __VA_ARGS__);            \
-  else hipLaunchKernelGGL((KERNEL<128>), grid, dim3(256), 0, s, __VA_ARGS__);
+// dynamic LDS of the dK/dV kernel; 0 = this problem stays on the 16x16 kernel (head dims above 96 spill there; very long sequences)
+int ivh_host::attn32_dkdv_lds_bytes(int Lq, int hd) {
+  if (hd > 96) return 0;
+  const int hdp = hd <= 64 ? 64 : 96;
+  const long bytes = 4L * 64 * hdp * 2 + (long)((Lq + 63) / 64) * 64 * 8;
+  return bytes <= 80 * 1024 ? (int)bytes : 0;            // two workgroups per CU
+}
 
-// measurement aid: a device buffer of [rows][4] uint64 receives wave 0's shader-clock stamps (entry, loop start, loop end, exit) of every
+// ---- process-wide measurement switches (internvideo_hip_debug.h); the routes of flash_attn.hip read them through attn32_switches()
+// a device buffer of [rows][4] uint64 receives wave 0's shader-clock stamps (entry, loop start, loop end, exit) of every
 // forward workgroup launched while it is set; NULL switches it off (the default).  Not thread-safe: a debugging facility.
 static unsigned long long* g_a32_stamps = nullptr;
 static long g_a32_stamp_rows = 0;
@@ -963,103 +966,79 @@ extern "C" int ivh_attn32_debug_stamps(void* buf, int64_t rows) {
   g_a32_stamp_rows = buf ? (long)rows : 0;
   return 0;
 }
-
 // unpacked fp32 arithmetic in the three 32x32 attention kernels: -1 = read IVH_ATTN_NOPK once (default on), 0 / 1 = ivh_probe_attn32_unpacked
 static int g_a32_np = -1;
-static bool a32_np() {
-  if (g_a32_np < 0) { const char* e = getenv("IVH_ATTN_NOPK"); g_a32_np = (e && e[0] == '0') ? 0 : 1; }
-  return g_a32_np == 1;
-}
 extern "C" int ivh_probe_attn32_unpacked(int on) { g_a32_np = on ? 1 : 0; return 0; }
-
-// measurement switch (internvideo_hip_debug.h): 0 = the one-group forward kernel, 1 / 2 = attn32pp_fwd_kernel; -1 = read IVH_ATTN_PP once
+// 0 = the one-group forward kernel, 1 .. 5 = two wave groups, 6 / 7 = one-group variants; -1 = read IVH_ATTN_PP once
 static int g_a32_pingpong = -1;
 extern "C" int ivh_probe_attn32_pingpong(int mode) {
   IVH_REQUIRE(mode >= 0 && mode <= 7, "ivh_probe_attn32_pingpong: 0 (off), 1 (two wave groups), 2 (+ raised priority), 3 (groups = even / odd waves), 4 / 5 (1 / 2 with unpacked softmax), 6 (one group, unpacked), 7 (6 at two waves per SIMD)");
   g_a32_pingpong = mode;
   return 0;
 }
-
-extern "C" int ivh_attn32_fwd_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                     const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                     uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse,
-                                     int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, const int32_t* nb_dev, void* stream) {
-  IVH_REQUIRE(((uintptr_t)out % 16) == 0, "flash_attn_fwd: out must be 16-byte aligned");
+Attn32Switches ivh_host::attn32_switches() {
+  static int defer = -1;                                   // measurement aid: deferred rescale (IVH_ATTN_DEFER=1)
   if (g_a32_pingpong < 0) { const char* e = getenv("IVH_ATTN_PP"); g_a32_pingpong = e ? atoi(e) : 0; }
-  IVH_REQUIRE(!g_a32_stamps || g_a32_pingpong > 0 || (long)((Lq + 127) / 128) * H * B <= g_a32_stamp_rows, "flash_attn_fwd: the stamp buffer holds %ld workgroups", g_a32_stamp_rows);
-  static int defer = -1;
+  if (g_a32_np < 0) { const char* e = getenv("IVH_ATTN_NOPK"); g_a32_np = (e && e[0] == '0') ? 0 : 1; }
   if (defer < 0) { const char* e = getenv("IVH_ATTN_DEFER"); defer = (e && e[0] == '1') ? 1 : 0; }
-  hipStream_t s = (hipStream_t)stream;
-  if (g_a32_pingpong > 0 && g_a32_pingpong < 6 && g_a32_stamps && hd > 64 && hd <= 96) {     // segment stamps of workgroup 0, waves 0 and 4: [2][256] (tools/probes/attn_pp_stamps.py)
-    IVH_REQUIRE(g_a32_stamp_rows >= 128, "flash_attn_fwd: the two-group stamp buffer holds 2 x 256 uint64");
-    dim3 grid2((unsigned)((long)((Lq + 255) / 256) * H * B), 1, 1);
-    if (g_a32_pingpong >= 4)
-      hipLaunchKernelGGL((attn32pp_fwd_np_kernel<96, false, true>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                         (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev, g_a32_stamps);
-    else
-    hipLaunchKernelGGL((attn32pp_fwd_kernel<96, false, false, true>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                       (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev, g_a32_stamps);
-    return ivh_host::check_launch("flash_attn_fwd (32x32, two wave groups, stamps)");
+  return Attn32Switches{g_a32_pingpong, g_a32_np == 1, defer == 1, g_a32_stamps != nullptr, g_a32_stamp_rows};
+}
+
+// ---- launches.  Every 32x32x16 instantiation that exists, once: taking the address instantiates the kernel, and a launch whose key has no row
+// is an error, never another flavour (the 16x16 table is flash_attn.hip's).  flags = the AttnFlag bits that are template arguments or kernel names.
+struct Attn32Row { int kind, hdp, flags; void* fn; };
+#define A32_FWD_ROWS(hdp) \
+  {ATTN_FWD, hdp, 0, (void*)&attn32_fwd_kernel<hdp, false>}, {ATTN_FWD, hdp, ATTN_DEFER, (void*)&attn32_fwd_kernel<hdp, true>}, {ATTN_FWD, hdp, ATTN_NP, (void*)&attn32_fwd_np_kernel<hdp>}, \
+      {ATTN_FWD2, hdp, 0, (void*)&attn32pp_fwd_kernel<hdp, false>}, {ATTN_FWD2, hdp, ATTN_PRIO, (void*)&attn32pp_fwd_kernel<hdp, true>}
+#define A32_BWD_ROWS(kind, K, hdp) {kind, hdp, 0, (void*)&K##_kernel<hdp>}, {kind, hdp, ATTN_NP, (void*)&K##_np_kernel<hdp>}
+static const Attn32Row attn32_table[] = {
+    A32_FWD_ROWS(64), A32_FWD_ROWS(96), A32_FWD_ROWS(128),
+    A32_BWD_ROWS(ATTN_DQ, attn32_bwd_dq, 64), A32_BWD_ROWS(ATTN_DQ, attn32_bwd_dq, 96), A32_BWD_ROWS(ATTN_DQ, attn32_bwd_dq, 128),
+    A32_BWD_ROWS(ATTN_DKDV, attn32_bwd_dkdv, 64), A32_BWD_ROWS(ATTN_DKDV, attn32_bwd_dkdv, 96),              // head dims above 96 would spill
+    // measurement variants, 64 < hd <= 96 only: deferred rescale unpacked, two waves per SIMD, the q/k-norm prototype; two wave groups as
+    // even / odd waves, stamping, unpacked (plain, raised priority, stamping)
+    {ATTN_FWD, 96, ATTN_NP | ATTN_DEFER, (void*)&attn32_fwd_np_kernel<96, true>}, {ATTN_FWD, 96, ATTN_NP2, (void*)&attn32_fwd_np2_kernel<96>},
+    {ATTN_FWD, 96, ATTN_QKN, (void*)&attn32_fwd_kernel<96, false, true>},
+    {ATTN_FWD2, 96, ATTN_GSEL, (void*)&attn32pp_fwd_kernel<96, false, true>}, {ATTN_FWD2, 96, ATTN_STAMP, (void*)&attn32pp_fwd_kernel<96, false, false, true>},
+    {ATTN_FWD2, 96, ATTN_NP, (void*)&attn32pp_fwd_np_kernel<96, false>}, {ATTN_FWD2, 96, ATTN_NP | ATTN_PRIO, (void*)&attn32pp_fwd_np_kernel<96, true>},
+    {ATTN_FWD2, 96, ATTN_NP | ATTN_STAMP, (void*)&attn32pp_fwd_np_kernel<96, false, true>},
+};
+#undef A32_BWD_ROWS
+#undef A32_FWD_ROWS
+
+int ivh_host::attn32_launch(const AttnArgs& a, const AttnLaunch& l) {
+  const int key = l.kind == ATTN_FWD ? l.flags & ~ATTN_STAMP : l.flags;    // the one-group forward stamps when it is handed the buffer: no build of its own
+  void* fn = nullptr;
+  for (const Attn32Row& row : attn32_table)
+    if (row.kind == l.kind && row.hdp == l.hdp && row.flags == key) fn = row.fn;
+  IVH_REQUIRE(fn, "%s: the 32x32 attention kernel of kind %d, HDP %d, flags 0x%x is not built", l.what, l.kind, l.hdp, l.flags);
+  static bool attr_set = false;
+  if (l.kind == ATTN_DKDV && !attr_set) {                  // the only kernels with dynamic LDS: up to 80 KiB = two workgroups per CU
+    for (const Attn32Row& row : attn32_table)
+      if (row.kind == ATTN_DKDV) (void)hipFuncSetAttribute(row.fn, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
+    attr_set = true;
   }
-  if (g_a32_pingpong == 7 && !g_a32_stamps && hd > 64 && hd <= 96) {                  // the shipped kernel at two waves per SIMD
-    dim3 grid1((unsigned)((long)((Lq + 127) / 128) * H * B), 1, 1);
-    hipLaunchKernelGGL((attn32_fwd_np2_kernel<96>), grid1, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                       (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, (unsigned long long*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, nb_dev);
-    return ivh_host::check_launch("flash_attn_fwd (32x32, two waves per SIMD)");
+  const dim3 grid(l.grid, 1, 1), block(l.block);
+  hipStream_t s = (hipStream_t)a.stream;
+  unsigned long long* stamps = (l.flags & ATTN_STAMP) ? g_a32_stamps : nullptr;
+  switch (l.kind) {
+    case ATTN_FWD:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn32_fwd_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.out, a.ob, a.ol, a.oh, a.lse, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, stamps, a.qkn_rq, a.qkn_rk, a.qkn_wqk, a.nb_dev);
+      break;
+    case ATTN_FWD2:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn32pp_fwd_kernel<64, false>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.out, a.ob, a.ol, a.oh, a.lse, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, a.nb_dev, stamps);
+      break;
+    case ATTN_DQ:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn32_bwd_dq_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.out, a.dout, a.ob, a.ol, a.oh, a.lse, a.delta, a.dq, a.dqb, a.dql, a.dqh, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, a.nb_dev);
+      break;
+    default:
+      hipLaunchKernelGGL(reinterpret_cast<decltype(&attn32_bwd_dkdv_kernel<64>)>(fn), grid, block, l.lds, s, a.q, a.qsb, a.qsl, a.qsh, a.k, a.v, a.sb, a.sl, a.sh,
+                         a.dout, a.ob, a.ol, a.oh, a.lse, a.delta, a.dk, a.dv, a.dsb, a.dsl, a.dsh, a.H, a.Lq, a.Lk, a.hd, a.scale, a.kv_len, a.nb_dev);
   }
-  if (g_a32_pingpong == 6 && !g_a32_stamps && hd > 64 && hd <= 96) {                  // the one-group kernel with unpacked softmax arithmetic
-    dim3 grid1((unsigned)((long)((Lq + 127) / 128) * H * B), 1, 1);
-    hipLaunchKernelGGL((attn32_fwd_np_kernel<96>), grid1, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                       (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, (unsigned long long*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, nb_dev);
-    return ivh_host::check_launch("flash_attn_fwd (32x32, unpacked softmax)");
-  }
-  if (g_a32_pingpong > 0 && g_a32_pingpong < 6 && !g_a32_stamps) {                   // two wave groups one phase apart (1: plain, 2: MFMA segments at raised priority)
-    dim3 grid2((unsigned)((long)((Lq + 255) / 256) * H * B), 1, 1);
-#define IVH_A32_PP(HDP, PR) hipLaunchKernelGGL((attn32pp_fwd_kernel<HDP, PR>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, \
-                                               (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev)
-    const bool pr = g_a32_pingpong == 2;
-    if ((g_a32_pingpong == 4 || g_a32_pingpong == 5) && hd > 64 && hd <= 96) {      // unpacked softmax arithmetic (5: + raised priority)
-      if (g_a32_pingpong == 4)
-        hipLaunchKernelGGL((attn32pp_fwd_np_kernel<96, false>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                           (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev);
-      else
-        hipLaunchKernelGGL((attn32pp_fwd_np_kernel<96, true>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                           (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev);
-      return ivh_host::check_launch("flash_attn_fwd (32x32, two wave groups, unpacked softmax)");
-    }
-    if (g_a32_pingpong == 3 && hd > 64 && hd <= 96) {
-      hipLaunchKernelGGL((attn32pp_fwd_kernel<96, false, true>), grid2, dim3(512), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                         (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, nb_dev);
-      return ivh_host::check_launch("flash_attn_fwd (32x32, two wave groups, alternating)");
-    }
-    if (hd <= 64) { if (pr) IVH_A32_PP(64, true); else IVH_A32_PP(64, false); }
-    else if (hd <= 96) { if (pr) IVH_A32_PP(96, true); else IVH_A32_PP(96, false); }
-    else { if (pr) IVH_A32_PP(128, true); else IVH_A32_PP(128, false); }
-#undef IVH_A32_PP
-    return ivh_host::check_launch("flash_attn_fwd (32x32, two wave groups)");
-  }
-  dim3 grid((unsigned)((long)((Lq + 127) / 128) * H * B), 1, 1);
-#define IVH_A32_FWD(HDP, DF) hipLaunchKernelGGL((attn32_fwd_kernel<HDP, DF>), grid, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, \
-                                                (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, g_a32_stamps, \
-                                                (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, nb_dev)
-#define IVH_A32_FWD_NP(HDP) hipLaunchKernelGGL((attn32_fwd_np_kernel<HDP>), grid, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, \
-                                               (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, g_a32_stamps, \
-                                               (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, nb_dev)
-  if (defer && a32_np() && hd > 64 && hd <= 96) {              // measurement aid: deferred rescale without packed fp32 (IVH_ATTN_DEFER=1)
-    hipLaunchKernelGGL((attn32_fwd_np_kernel<96, true>), grid, dim3(256), 0, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                       (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, kv_len, g_a32_stamps,
-                       (const float*)nullptr, (const float*)nullptr, (const float*)nullptr, nb_dev);
-    return ivh_host::check_launch("flash_attn_fwd (32x32, deferred rescale)");
-  }
-  const bool np = a32_np() && !defer;
-  if (hd <= 64) { if (np) IVH_A32_FWD_NP(64); else if (defer) IVH_A32_FWD(64, true); else IVH_A32_FWD(64, false); }
-  else if (hd <= 96) { if (np) IVH_A32_FWD_NP(96); else if (defer) IVH_A32_FWD(96, true); else IVH_A32_FWD(96, false); }
-  else { if (np) IVH_A32_FWD_NP(128); else if (defer) IVH_A32_FWD(128, true); else IVH_A32_FWD(128, false); }
-#undef IVH_A32_FWD
-#undef IVH_A32_FWD_NP
-  return ivh_host::check_launch("flash_attn_fwd (32x32)");
+  return check_launch(l.what);
 }
 
 // round-5 prototype (internvideo_hip_debug.h): the forward kernel with the q/k RMSNorm applied on the fly -- q, k un-normalised, rq / rk fp32 [B * L]
@@ -1068,63 +1047,10 @@ extern "C" int ivh_probe_attn32_fwd_qkn(const uint16_t* q, int64_t qsb, int64_t 
                                         const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
                                         uint16_t* out, int64_t ob, int64_t ol, int64_t oh, float* lse,
                                         int B, int H, int Lq, int Lk, int hd, float scale, const float* rq, const float* rk, const float* wqk, void* stream) {
+  AttnArgs a = attn_args(q, qsb, qsl, qsh, k, v, sb, sl, sh, ob, ol, oh, B, H, Lq, Lk, hd, scale, nullptr, stream);
+  a.out = out; a.lse = lse;
+  a.qkn_rq = rq; a.qkn_rk = rk; a.qkn_wqk = wqk;
   IVH_REQUIRE(rq && rk && wqk && hd > 64 && hd <= 96 && hd % 8 == 0 && Lk <= 512 && Lq == Lk, "probe_attn32_fwd_qkn: prototype for 64 < hd <= 96, Lq == Lk <= 512");
-  IVH_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)wqk % 16) == 0 && ivh_attn32_supported(qsb, qsl, qsh, sb, sl, sh, ob, ol, oh, Lq, Lk, hd), "probe_attn32_fwd_qkn: layout");
-  dim3 grid((unsigned)((long)((Lq + 127) / 128) * H * B), 1, 1);
-  hipLaunchKernelGGL((attn32_fwd_kernel<96, false, true>), grid, dim3(256), 0, (hipStream_t)stream, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl,
-                     (long)sh, out, (long)ob, (long)ol, (long)oh, lse, H, Lq, Lk, hd, scale, (const int32_t*)nullptr, (unsigned long long*)nullptr, rq, rk, wqk);
-  return ivh_host::check_launch("probe_attn32_fwd_qkn");
-}
-
-// dQ (+ delta) part of the backward
-extern "C" int ivh_attn32_bwd_dq_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                        const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                        const uint16_t* out, const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh,
-                                        const float* lse, float* delta, uint16_t* dq, int64_t dqb, int64_t dql, int64_t dqh,
-                                        int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, const int32_t* nb_dev, void* stream) {
-  IVH_REQUIRE(((uintptr_t)dq % 16) == 0 && dqb % 8 == 0 && dql % 8 == 0 && dqh % 8 == 0, "flash_attn_bwd: dq must be 16-byte aligned with strides that are multiples of 8");
-  dim3 gq((unsigned)((long)((Lq + 127) / 128) * H * B), 1, 1);
-  if (a32_np()) {
-    IVH_ATTN32_DISPATCH(hd, attn32_bwd_dq_np_kernel, gq, (hipStream_t)stream, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, out, dout,
-                        (long)ob, (long)ol, (long)oh, lse, delta, dq, (long)dqb, (long)dql, (long)dqh, H, Lq, Lk, hd, scale, kv_len, nb_dev);
-  } else {
-    IVH_ATTN32_DISPATCH(hd, attn32_bwd_dq_kernel, gq, (hipStream_t)stream, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, out, dout,
-                        (long)ob, (long)ol, (long)oh, lse, delta, dq, (long)dqb, (long)dql, (long)dqh, H, Lq, Lk, hd, scale, kv_len, nb_dev);
-  }
-  return ivh_host::check_launch("flash_attn_bwd dq (32x32)");
-}
-
-// dynamic LDS of the dK/dV kernel; 0 = this problem stays on the 16x16 kernel (head dims above 96 spill there; very long sequences)
-extern "C" int ivh_attn32_dkdv_lds_bytes(int Lq, int hd) {
-  if (hd > 96) return 0;
-  const int hdp = hd <= 64 ? 64 : 96;
-  const long bytes = 4L * 64 * hdp * 2 + (long)((Lq + 63) / 64) * 64 * 8;
-  return bytes <= 80 * 1024 ? (int)bytes : 0;            // two workgroups per CU
-}
-
-extern "C" int ivh_attn32_bwd_dkdv_launch(const uint16_t* q, int64_t qsb, int64_t qsl, int64_t qsh,
-                                          const uint16_t* k, const uint16_t* v, int64_t sb, int64_t sl, int64_t sh,
-                                          const uint16_t* dout, int64_t ob, int64_t ol, int64_t oh, const float* lse, const float* delta,
-                                          uint16_t* dk, uint16_t* dv, int64_t dsb, int64_t dsl, int64_t dsh,
-                                          int B, int H, int Lq, int Lk, int hd, float scale, const int32_t* kv_len, const int32_t* nb_dev, void* stream) {
-  const int lds_bytes = ivh_attn32_dkdv_lds_bytes(Lq, hd);
-  IVH_REQUIRE(lds_bytes > 0, "flash_attn_bwd dkdv (32x32): unsupported head dim / sequence length");
-  IVH_REQUIRE(((uintptr_t)dk % 16) == 0 && ((uintptr_t)dv % 16) == 0 && dsb % 8 == 0 && dsl % 8 == 0 && dsh % 8 == 0,
-              "flash_attn_bwd: dk / dv must be 16-byte aligned with strides that are multiples of 8");
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)attn32_bwd_dkdv_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn32_bwd_dkdv_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn32_bwd_dkdv_np_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    (void)hipFuncSetAttribute((const void*)attn32_bwd_dkdv_np_kernel<96>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024);
-    attr_set = true;
-  }
-  dim3 gk((unsigned)((long)((Lk + 127) / 128) * H * B), 1, 1);
-  hipStream_t s = (hipStream_t)stream;
-#define IVH_A32_DKDV(KERNEL) hipLaunchKernelGGL((KERNEL), gk, dim3(256), lds_bytes, s, q, (long)qsb, (long)qsl, (long)qsh, k, v, (long)sb, (long)sl, (long)sh, dout, \
-                                                (long)ob, (long)ol, (long)oh, lse, delta, dk, dv, (long)dsb, (long)dsl, (long)dsh, H, Lq, Lk, hd, scale, kv_len, nb_dev)
-  if (a32_np()) { if (hd <= 64) IVH_A32_DKDV(attn32_bwd_dkdv_np_kernel<64>); else IVH_A32_DKDV(attn32_bwd_dkdv_np_kernel<96>); }
-  else { if (hd <= 64) IVH_A32_DKDV(attn32_bwd_dkdv_kernel<64>); else IVH_A32_DKDV(attn32_bwd_dkdv_kernel<96>); }
-#undef IVH_A32_DKDV
-  return ivh_host::check_launch("flash_attn_bwd dkdv (32x32)");
+  IVH_REQUIRE(((uintptr_t)out % 16) == 0 && ((uintptr_t)wqk % 16) == 0 && attn32_supported(a), "probe_attn32_fwd_qkn: layout");
+  return attn32_launch(a, AttnLaunch{32, ATTN_FWD, 96, ATTN_QKN, (unsigned)((long)((Lq + 127) / 128) * H * B), 256, 0, "probe_attn32_fwd_qkn"});
 }

@@ -50,10 +50,6 @@ SIGNATURES = {
     "ivh_colsum_finish_dyn": [_vp, _i32, _i32, _vp, _i32, _vp, _i32, _i32, _vp],
     "ivh_qk_rmsnorm_fwd_dyn": [_vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp],
     "ivh_qk_rmsnorm_bwd_dyn": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp],
-    "ivh_flash_attn_fwd_dyn": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
-                               _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp],
-    "ivh_flash_attn_bwd_dyn": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                               _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp],
     "ivh_set_dropout_epoch": [_vp],
     "ivh_device_info": [C.POINTER(_i32), C.POINTER(_i32), C.c_char_p, _i32],
     "ivh_gemm_bf16": [C.POINTER(GemmDesc), _vp],
@@ -77,6 +73,7 @@ SIGNATURES = {
     "ivh_gemm256_debug_half": [_i32],
     "ivh_gemm256_debug_route": [C.POINTER(GemmDesc), _i32, _i32, C.POINTER(_i32)],
     "ivh_rmsnorm_add_debug_route": [_i32, _i32, _u32, _i32, _i32, _i32, C.POINTER(_i32)],
+    "ivh_attn_debug_route": [_i32, _i32, C.POINTER(C.c_uint64), C.POINTER(_i64), _i32, _i32, _i32, _i32, _i32, _i32, C.POINTER(_i32)],
     "ivh_gemm256_half_rounds": [C.POINTER(GemmDesc)],
     "ivh_attn32_debug_stamps": [_vp, _i64],
     "ivh_gemm_split_workspace": [C.POINTER(GemmDesc)],
@@ -94,14 +91,6 @@ SIGNATURES = {
     "ivh_colsum_scratch_floats": [_i32, _i32],
     "ivh_qk_rmsnorm_fwd": [_vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp],
     "ivh_qk_rmsnorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
-    "ivh_flash_attn_fwd": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
-                           _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
-    "ivh_flash_attn_bwd": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                           _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp],
-    "ivh_flash_attn_fwd_dropout": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
-                                   _i32, _i32, _i32, _i32, _i32, _f32, _vp, _f32, _u32, _vp],
-    "ivh_flash_attn_bwd_dropout": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp,
-                                   _vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _f32, _u32, _vp],
     "ivh_set_attn_kernel": [_i32],
     "ivh_mask_to_indices": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
     "ivh_patch_im2col": [_vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
@@ -172,9 +161,16 @@ SIGNATURES = {
     "ivh_probe_mfma_rate2": [_i32, _i32, _i32, _i32, _vp, _vp],
     "ivh_probe_attn32_pingpong": [_i32],
     "ivh_probe_attn32_unpacked": [_i32],
-    "ivh_probe_attn32_fwd_qkn": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _i64, _i64, _vp,
-                                 _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
 }
+# The attention entry points share one argument list: (pointer, three strides) groups, then B, H, Lq, Lk, hd, scale, kv_len, and a tail by flavour
+_PS = [_vp, _i64, _i64, _i64]
+_ATTN_QKV = _PS + [_vp] + _PS                                                   # q + strides; k, v + the strides they share
+_ATTN_HEAD = {"fwd": _ATTN_QKV + _PS + [_vp],                                   # out + strides, lse
+              "bwd": _ATTN_QKV + [_vp] + _PS + [_vp, _vp] + _PS + [_vp] + _PS}  # out, dout + strides, lse, delta, dq + strides, dk, dv + strides
+_ATTN_DIMS = [_i32] * 5 + [_f32, _vp]                                           # B, H, Lq, Lk, hd, scale, kv_len
+_ATTN_TAIL = {"": [_vp], "_dyn": [_vp, _vp], "_dropout": [_f32, _u32, _vp]}     # [nb_dev | p_drop, seed,] stream
+SIGNATURES.update({f"ivh_flash_attn_{d}{sfx}": head + _ATTN_DIMS + tail for d, head in _ATTN_HEAD.items() for sfx, tail in _ATTN_TAIL.items()})
+SIGNATURES["ivh_probe_attn32_fwd_qkn"] = _ATTN_HEAD["fwd"] + _ATTN_DIMS[:-1] + [_vp] * 4      # no kv_len; rq, rk, wqk, stream
 _RESTYPES = {"ivh_last_error": C.c_char_p, "ivh_vtc_workspace_floats": C.c_int64, "ivh_rerank_lists_workspace_bytes": C.c_int64, "ivh_gemm_split_workspace": C.c_int64, "ivh_gemm_fp8_split_workspace": C.c_int64,
              "ivh_gemm256_half_rounds": C.c_double}
 

@@ -577,6 +577,21 @@ def _kv_len(kv_len: Optional[torch.Tensor], B: int) -> Optional[torch.Tensor]:
     return kv_len
 
 
+def _attn_call(direction: str, args: tuple, B: int, kv_len, drop_p: float, seed: int, nb_dev=None, flop: Optional[float] = None) -> None:
+    """ivh_flash_attn_{fwd,bwd}{,_dyn,_dropout} on `args` (everything up to scale): the one place that picks the entry point and appends its tail.
+    flop: the launch is timed under bench.py's kernel profile (the packed wrappers; the dropout entries are not)."""
+    name = "flash_attn_" + direction
+    args = (*args, ptr(_kv_len(kv_len, B)))
+    if drop_p > 0:
+        call(f"ivh_{name}_dropout", *args, float(drop_p), int(seed) & 0xFFFFFFFF, stream_ptr())
+    elif nb_dev is not None:                                # only the first *nb_dev clips exist (DropPath skipping); the rest of the outputs is untouched
+        _pcall(name, flop, "FLOP", f"ivh_{name}_dyn", *args, ptr(_cnt(nb_dev, "nb_dev")), stream_ptr(), dyn=(nb_dev, B))
+    elif flop is not None:
+        _pcall(name, flop, "FLOP", f"ivh_{name}", *args, stream_ptr())
+    else:
+        call(f"ivh_{name}", *args, stream_ptr())
+
+
 def flash_attn_fwd_packed(qkv: torch.Tensor, B: int, L: int, H: int, scale: Optional[float] = None,
                           kv_len: Optional[torch.Tensor] = None, drop_p: float = 0.0, seed: int = 0, nb_dev: Optional[torch.Tensor] = None):
     """qkv: [B*L, 3*H*hd] bf16 packed (three, head, d) -> (out [B*L, H*hd] bf16, lse [B,H,L] fp32).
@@ -592,16 +607,8 @@ def flash_attn_fwd_packed(qkv: torch.Tensor, B: int, L: int, H: int, scale: Opti
     out = torch.empty((M, D), dtype=BF16, device=qkv.device)
     lse = torch.empty((B, H, L), dtype=F32, device=qkv.device)
     q, k, v = qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2
-    if drop_p > 0:
-        call("ivh_flash_attn_fwd_dropout", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), L * D, D, hd, ptr(lse),
-             B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)), float(drop_p), int(seed) & 0xFFFFFFFF, stream_ptr())
-        return out, lse
-    if nb_dev is not None:                                  # only the first *nb_dev clips exist (DropPath skipping); the rest of out / lse is untouched
-        _pcall("flash_attn_fwd", 4.0 * B * H * L * L * hd, "FLOP", "ivh_flash_attn_fwd_dyn", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), L * D, D, hd, ptr(lse),
-               B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)), ptr(_cnt(nb_dev, "nb_dev")), stream_ptr(), dyn=(nb_dev, B))
-        return out, lse
-    _pcall("flash_attn_fwd", 4.0 * B * H * L * L * hd, "FLOP", "ivh_flash_attn_fwd", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), L * D, D, hd, ptr(lse),
-           B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)), stream_ptr())
+    _attn_call("fwd", (q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), L * D, D, hd, ptr(lse), B, H, L, L, hd, scale),
+               B, kv_len, drop_p, seed, nb_dev, flop=4.0 * B * H * L * L * hd)
     return out, lse
 
 
@@ -621,18 +628,9 @@ def flash_attn_bwd_packed(qkv: torch.Tensor, out: torch.Tensor, dout: torch.Tens
     delta = torch.empty((B, H, L), dtype=F32, device=qkv.device)
     q, k, v = qkv.data_ptr(), qkv.data_ptr() + D * 2, qkv.data_ptr() + 2 * D * 2
     dq, dk, dv = dqkv.data_ptr(), dqkv.data_ptr() + D * 2, dqkv.data_ptr() + 2 * D * 2
-    if drop_p > 0:
-        call("ivh_flash_attn_bwd_dropout", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), ptr(dout), L * D, D, hd,
-             ptr(lse), ptr(delta), dq, L * D3, D3, hd, dk, dv, L * D3, D3, hd, B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)),
-             float(drop_p), int(seed) & 0xFFFFFFFF, stream_ptr())
-        return dqkv
-    if nb_dev is not None:
-        _pcall("flash_attn_bwd", 10.0 * B * H * L * L * hd, "FLOP", "ivh_flash_attn_bwd_dyn", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), ptr(dout), L * D, D, hd,
-               ptr(lse), ptr(delta), dq, L * D3, D3, hd, dk, dv, L * D3, D3, hd, B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)), ptr(_cnt(nb_dev, "nb_dev")),
-               stream_ptr(), dyn=(nb_dev, B))
-        return dqkv
-    _pcall("flash_attn_bwd", 10.0 * B * H * L * L * hd, "FLOP", "ivh_flash_attn_bwd", q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), ptr(dout), L * D, D, hd,
-           ptr(lse), ptr(delta), dq, L * D3, D3, hd, dk, dv, L * D3, D3, hd, B, H, L, L, hd, scale, ptr(_kv_len(kv_len, B)), stream_ptr())
+    _attn_call("bwd", (q, L * D3, D3, hd, k, v, L * D3, D3, hd, ptr(out), ptr(dout), L * D, D, hd, ptr(lse), ptr(delta),
+                       dq, L * D3, D3, hd, dk, dv, L * D3, D3, hd, B, H, L, L, hd, scale),
+               B, kv_len, drop_p, seed, nb_dev, flop=10.0 * B * H * L * L * hd)
     return dqkv
 
 
@@ -655,13 +653,8 @@ def flash_attn_fwd(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: Opt
     scale = float(hd ** -0.5 if scale is None else scale)
     out = torch.empty((B, Lq, H, hd), dtype=BF16, device=q.device)
     lse = torch.empty((B, H, Lq), dtype=F32, device=q.device)
-    if drop_p > 0:
-        call("ivh_flash_attn_fwd_dropout", ptr(q), q.stride(0), q.stride(1), q.stride(2), ptr(k), ptr(v), k.stride(0), k.stride(1), k.stride(2),
-             ptr(out), out.stride(0), out.stride(1), out.stride(2), ptr(lse), B, H, Lq, Lk, hd, scale, ptr(_kv_len(kv_len, B)),
-             float(drop_p), int(seed) & 0xFFFFFFFF, stream_ptr())
-        return out, lse
-    call("ivh_flash_attn_fwd", ptr(q), q.stride(0), q.stride(1), q.stride(2), ptr(k), ptr(v), k.stride(0), k.stride(1), k.stride(2),
-         ptr(out), out.stride(0), out.stride(1), out.stride(2), ptr(lse), B, H, Lq, Lk, hd, scale, ptr(_kv_len(kv_len, B)), stream_ptr())
+    _attn_call("fwd", (ptr(q), *q.stride()[:3], ptr(k), ptr(v), *k.stride()[:3], ptr(out), *out.stride()[:3], ptr(lse), B, H, Lq, Lk, hd, scale),
+               B, kv_len, drop_p, seed)
     return out, lse
 
 
@@ -677,14 +670,9 @@ def flash_attn_bwd(q, k, v, out, dout, lse, scale: Optional[float] = None, kv_le
     dq = torch.empty((B, Lq, H, hd), dtype=BF16, device=q.device)
     dkv = torch.empty((2, B, Lk, H, hd), dtype=BF16, device=q.device)
     delta = torch.empty((B, H, Lq), dtype=F32, device=q.device)
-    args = (ptr(q), q.stride(0), q.stride(1), q.stride(2), ptr(k), ptr(v), k.stride(0), k.stride(1), k.stride(2),
-            ptr(out), ptr(dout), out.stride(0), out.stride(1), out.stride(2), ptr(lse), ptr(delta),
-            ptr(dq), dq.stride(0), dq.stride(1), dq.stride(2), ptr(dkv[0]), ptr(dkv[1]), dkv.stride(1), dkv.stride(2), dkv.stride(3),
-            B, H, Lq, Lk, hd, scale, ptr(_kv_len(kv_len, B)))
-    if drop_p > 0:
-        call("ivh_flash_attn_bwd_dropout", *args, float(drop_p), int(seed) & 0xFFFFFFFF, stream_ptr())
-    else:
-        call("ivh_flash_attn_bwd", *args, stream_ptr())
+    _attn_call("bwd", (ptr(q), *q.stride()[:3], ptr(k), ptr(v), *k.stride()[:3], ptr(out), ptr(dout), *out.stride()[:3], ptr(lse), ptr(delta),
+                       ptr(dq), *dq.stride()[:3], ptr(dkv[0]), ptr(dkv[1]), *dkv.stride()[1:4], B, H, Lq, Lk, hd, scale),
+               B, kv_len, drop_p, seed)
     return dq, dkv
 
 
